@@ -18,6 +18,20 @@ cadence (the driver's 20 turns: one 20-row exchange, then one 20-turn launch;
 config.exchanges_timed, per-rank exchange times in config.exchange_us_per_rank, and the
 stencil alone, with no exchange timed, in config.compute_only).
 
+A plain run (`--gpus N --steps K --warmup W`) sets up the headline board, warms up, times the
+K turns, writes its outputs when `--dump-outputs DIR` is given and prints the result line:
+nothing else runs on the GPU or the CPU.  `--full` adds every other measurement described
+below (the cold first call, `compute_only`, `configs_measured`, `cpu_baseline`).
+
+`--dump-outputs DIR` writes what the timed path left after its last timed turn, read back
+through the engine's own calls (gol_read_packed, gol_snapshot), as DIR/<name>.npy (at N > 1
+each rank writes its strip as <name>_rank<r>.npy):
+  * alive: float64 [completed turns, alive cells];
+  * row_alive: float64, the alive cells of every row (every cell of the board counts);
+  * sample_rows, cells_sample: float64 row numbers of a fixed, seeded sample of rows (at most
+    32 MiB of cells) and those rows' cells as float32 0/1, column 0 first.
+The board is the seeded generator's, so two runs with the same arguments hold the same inputs.
+
 Printed (rank 0): one JSON line with the driver's contract fields plus
 `roofline` (the dominant kernel's algorithmic HBM bytes per launch -- one read + one
 write of the packed board, 0.25/k B per cell-update for k fused turns -- per average
@@ -25,7 +39,8 @@ launch time, vs 8 TB/s; PMC-measured bytes in `traffic`), `k1_equivalent` (the k
 bytes of SURVEY 8(d), which exceed any HBM roof once k > 1), `valu_roofline` (the
 binding roof of the blocked kernel: the 52-cycle VALU issue model, at 2.4 GHz and at the
 clock measured under load, with the kernel's SIMD cycles per VALU and its VALU inflation
-from the SQ pass of the same launch), `configs_measured` and `cpu_baseline`:
+from the SQ pass of the same launch) and, with `--full`, `configs_measured` and
+`cpu_baseline`:
   * config.create_ms: the engine's create time (the first engine of a pinned shape in a
     process also runs ~60 ms of its launches: gol_engine.cpp check_pinned);
     config.cold_first_call (N = 1): the same 20 turns in an engine created with that check
@@ -91,6 +106,13 @@ def parse():
     ap.add_argument("--band", type=int, default=0, help="stencil band rows (0 = auto)")
     ap.add_argument("--tpl", type=int, default=0,
                     help="turns per stencil launch (temporal blocking; 0 = engine default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: the cold first call, "
+                         "the no-exchange rate (N > 1), the other BASELINE configs and the CPU "
+                         "baseline (the --no-* / --c*-size options below then pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the board they left (alive count, "
+                         "per-row alive counts, a seeded sample of rows) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-turns", type=int, default=2)
     ap.add_argument("--cpu-cores", type=int, default=0,
@@ -182,7 +204,7 @@ def cpu_baseline(size, seed, turns, cores):
 
 
 def measure(a, size, steps, warmup, world, rank, gpu, dev, dev_ids, stream, seed=None,
-            snapshot=False, halo=None, compute_only=False):
+            snapshot=False, halo=None, compute_only=False, whole_window=False, dump_dir=None):
     """Time `steps` turns of one size x size torus board (whole board at N = 1, this rank's
     row strip at N > 1) after `warmup` turns.  `snapshot`: the AliveCellsCount pair of the
     final turn (gol_snapshot) is taken inside the timed region.
@@ -192,8 +214,10 @@ def measure(a, size, steps, warmup, world, rank, gpu, dev, dev_ids, stream, seed
     exchange), so it holds ceil(steps / halo) exchanges -- one per `halo` turns, the cadence of
     the run -- each bracketed by HIP events (per-rank exchange time).  `compute_only`: then
     time the same strip again over min(steps, halo) turns right after an untimed exchange (no
-    exchange inside: the stencil alone, a labelled secondary figure).  Returns the timing and
-    roofline inputs."""
+    exchange inside: the stencil alone, a labelled secondary figure).  `whole_window`: when
+    the last timed gol_step was a partial window, run one more whole window, untimed, and take
+    the launch shape from it.  `dump_dir`: write the board the timed turns left
+    (dump_outputs), before anything else steps it.  Returns the timing and roofline inputs."""
     seed = a.seed if seed is None else seed
     import gol
     from gol.distributed import DistStrip, EngineStrip, make_engine_strip
@@ -275,7 +299,9 @@ def measure(a, size, steps, warmup, world, rank, gpu, dev, dev_ids, stream, seed
     launches = info.launches - launches0
     exchanges = getattr(runner, "exchanges", 0) - exchanges0
     xus = runner.exchange_us() if world > 1 else []
-    if world > 1 and steps > eng.halo:
+    if dump_dir:
+        dump_outputs(eng, dump_dir, rank, world)
+    if whole_window and world > 1 and steps > eng.halo:
         # the timed region's last gol_step ran only the last (partial) window: take the launch
         # shape from one more whole window, untimed (every rank: it exchanges first)
         runner.start_window()
@@ -330,6 +356,31 @@ def measure(a, size, steps, warmup, world, rank, gpu, dev, dev_ids, stream, seed
            "exchange_us": xus, "compute_only": comp}
     eng.close()
     return out
+
+
+DUMP_SAMPLE_BYTES = 32 << 20   # float32 cells of the sampled rows, at most
+DUMP_SAMPLE_SEED = 20
+
+
+def dump_outputs(eng, out_dir, rank, world):
+    """--dump-outputs: the board as a caller of the timed path reads it back (gol_snapshot,
+    gol_read_packed; at N > 1 this rank's own rows), as float arrays in out_dir."""
+    import numpy as np
+    turn, alive = eng.snapshot()
+    words = eng.read_packed()                       # (rows, words per row) uint64, bit x % 64
+    rows, W = words.shape[0], eng.width
+    row_alive = np.bitwise_count(words).sum(axis=1, dtype=np.int64)
+    n = max(1, min(rows, DUMP_SAMPLE_BYTES // (4 * W)))
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=n, replace=False))
+    bits = np.unpackbits(np.ascontiguousarray(words[pick]).view(np.uint8), axis=1,
+                         bitorder="little")[:, :W]
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("alive", np.array([turn, alive], dtype=np.float64)),
+                      ("row_alive", row_alive.astype(np.float64)),
+                      ("sample_rows", pick.astype(np.float64)),
+                      ("cells_sample", bits.astype(np.float32))):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
 
 
 def measure_cold(a, gpu, stream):
@@ -591,23 +642,24 @@ def main():
         # grid per device at a time; the engine cannot see other processes' grids)
         os.environ["GOL_SHARED_DEVICE"] = "1"
     cold = None
-    if world == 1 and not a.no_cold:
+    if a.full and world == 1 and not a.no_cold:
         cold = measure_cold(a, gpu, stream)
     # N > 1: halo = turns between exchanges; by default the deepest whose windows the timed
     # turns hold whole (the driver's 20 turns: one 20-row exchange, then one 20-turn launch)
     halo = a.halo or min(HALO_MAX, a.steps)
     m = measure(a, a.size, a.steps, a.warmup, world, rank, gpu, dev, dev_ids, stream, halo=halo,
-                compute_only=True)
+                compute_only=a.full, whole_window=a.full, dump_dir=a.dump_outputs)
     c3 = None
     # (BASELINE configs[2] is quoted on 1 and 2 GPUs)
-    if a.c3_size > 0 and a.c3_size != a.size and world <= 2:
+    if a.full and a.c3_size > 0 and a.c3_size != a.size and world <= 2:
         c3 = measure(a, a.c3_size, a.c3_turns, max(a.warmup, 60), world, rank, gpu, dev,
-                     dev_ids, stream, halo=a.halo or min(HALO_MAX, a.c3_turns))
+                     dev_ids, stream, halo=a.halo or min(HALO_MAX, a.c3_turns),
+                     whole_window=True)
     c2 = None
-    if world == 1 and a.c2_size > 0 and a.c2_size != a.size:
+    if a.full and world == 1 and a.c2_size > 0 and a.c2_size != a.size:
         c2 = measure(a, a.c2_size, a.c2_turns, max(a.warmup, 64), world, rank, gpu, dev,
                      dev_ids, stream, seed=1, snapshot=True)
-    c1 = measure_c1(gpu, stream) if world == 1 and not a.no_c1 else None
+    c1 = measure_c1(gpu, stream) if a.full and world == 1 and not a.no_c1 else None
 
     if rank == 0:
         W, H, K = m["W"], m["H"], m["K"]
@@ -727,7 +779,7 @@ def main():
             cm.append(c1)
         if cm:
             out["configs_measured"] = cm
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, a.seed, a.cpu_turns, a.cpu_cores)
             if not a.no_c1:
                 share, aff, omp = cpu_share()

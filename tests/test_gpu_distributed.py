@@ -137,8 +137,9 @@ def _bench_line(stdout):
 
 
 def test_bench_contract_one_gpu():
-    """bench.py's single JSON line (driver contract) at a small size, CPU baseline included."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "4096",
+    """bench.py --full's single JSON line (driver contract) at a small size, CPU baseline
+    included."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--size", "4096",
                         "--steps", "64", "--warmup", "8", "--cpu-turns", "1",
                         "--c3-size", "2048", "--c3-turns", "96"],
                        capture_output=True, text=True, timeout=240)
@@ -165,6 +166,42 @@ def test_bench_contract_one_gpu():
     assert f"{cb['cores']} OpenMP threads" in cb["sample"]
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain bench run measures the headline only (no cold call, other configs or CPU
+    baseline) and --dump-outputs writes the board its timed turns left: checked against the
+    oracle after warm-up + steps turns of the same seeded board (1088 x 1088: 17 words per
+    row; the row sample holds every row of a board this small)."""
+    import numpy as np
+    from oracle import oracle as O
+    size, steps, warmup, seed = 1088, 37, 5, 3
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size",
+                        str(size), "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _bench_line(p.stdout)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GCUPS"
+    # value and ms_per_step are one measurement (rounded to 0.01 GCUPS and 1e-5 ms)
+    rel = 0.5e-5 / d["ms_per_step"] + 0.005 / d["value"] + 1e-6
+    assert abs(d["value"] * d["ms_per_step"] / (size * size / 1e6) - 1) <= 1.1 * rel
+    assert d["cpu_baseline"] is None and "configs_measured" not in d
+    assert "cold_first_call" not in d["config"]
+    want = O.unpack(O.bit_run(O.gen_random(seed, size, size), size, steps + warmup), size) // 255
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("alive", "row_alive", "sample_rows",
+                                                       "cells_sample")}
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{n}.npy" for n in got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["alive"].tolist() == [steps + warmup, int(want.sum())]
+    assert np.array_equal(got["row_alive"], want.sum(axis=1))
+    rows = got["sample_rows"].astype(np.int64)
+    assert np.array_equal(rows, np.arange(size))        # (32 MiB hold every row of this board)
+    assert got["cells_sample"].dtype == np.float32
+    assert np.array_equal(got["cells_sample"], want[rows])
+
+
 @pytest.mark.parametrize("size,steps,halo,exchanges,c3", [(65536, 20, None, 1, 16384),
                                                          (4096, 64, 16, 4, 2048)])
 def test_bench_torchrun_two_ranks_gloo(size, steps, halo, exchanges, c3):
@@ -178,7 +215,7 @@ def test_bench_torchrun_two_ranks_gloo(size, steps, halo, exchanges, c3):
     not of the run's last partial one)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={29611 + steps}",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", str(size), "--steps",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--size", str(size), "--steps",
            str(steps), "--warmup", "5", "--backend", "gloo", "--c3-size", str(c3),
            "--c3-turns", "300" if c3 == 16384 else "40"] + (["--halo", str(halo)] if halo else [])
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240,

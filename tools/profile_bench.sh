@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiles that reproduce the bench line (ROUND=r05 names the pass: gpurun_out/prof_$ROUND,
 # then tools/summarize_bench.sh writes profiles/${ROUND}_k{K}_{size}_{name}_summary.json): (1) the bench exactly as the driver runs it
-# (bench.py --gpus 1 --steps 20 --warmup 5, all configs) under --kernel-trace --stats; (2) for
+# (bench.py --full --gpus 1 --steps 20 --warmup 5, all configs) under --kernel-trace --stats; (2) for
 # the headline board, C3 and C2, the launch shape the bench reports (config.launch_shape /
 # configs_measured[i].launch_shape), pinned in tools/kernel_run.py (no autotune), under a
 # FETCH_SIZE pass, a WRITE_SIZE pass, a kernel trace and an SQ / GRBM pass (clock under load,
@@ -26,7 +26,7 @@ if [ "${ONLY_EXTRA:-0}" = 1 ]; then
   BL="$O/bench_line_extra.json"
 else
   run kt 400 --kernel-trace --stats -d "$O/kt" -o run --output-format csv -- \
-      python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-cold
+      python3 "$R/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-cold
   grep '^{"metric"' "$O/kt.log" > "$O/bench_line.json" || { echo "no bench line"; exit 1; }
   BL="$O/bench_line.json"
 fi
