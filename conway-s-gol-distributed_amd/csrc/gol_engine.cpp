@@ -10,7 +10,7 @@
 //   blocked    packed mask of the cells that were neither 0 nor 255 at load
 //              (only while turn 1 is pending; reference quirk,
 //              SubServer/distributor.go:178-200 + :122-125)
-//   counts     popcount shards (kShards u64) x kRing slots for the per-turn
+//   counts     popcount shards (kShards u64) x kRingSlots slots for the per-turn
 //              series (GOL_FLAG_COUNT_EVERY_TURN) and one slot for snapshots
 //   staging    byte / alive-list staging, allocated on demand
 #include <hip/hip_runtime.h>
@@ -42,8 +42,23 @@ using golk::kShards;
 
 namespace {
 
-constexpr int kRing = 4096;                 // per-turn count ring (turn t -> slot t % kRing)
-constexpr size_t kStagingBytes = 256u << 20;  // byte staging chunk for load / read
+constexpr int kRing = 4096;                 // per-turn counts kept: gol_turn_counts' window
+// The ring has kRingAhead more slots than the window (turn t -> slot t % kRingSlots): a step
+// zeroes the slots of up to kRingAhead coming turns in one memset, and those slots hold turns
+// <= turn + kRingAhead - kRingSlots = turn - kRing, already outside the window.  So a reader
+// served in the middle of a step, or after a step that GOL_CONTROL_STOP cut short, never sees
+// a zeroed slot for a turn the window accepts.
+constexpr int kRingAhead = 256;
+constexpr int kRingSlots = kRing + kRingAhead;
+static_assert(kRingSlots % kRingAhead == 0, "a batch of zeroed slots never wraps the ring");
+// byte staging chunk for load / read and the alive list (a test build shrinks it so that small
+// boards take several chunks: make smallstage)
+#ifndef GOL_STAGING_BYTES
+#define GOL_STAGING_BYTES (256u << 20)
+#endif
+constexpr size_t kStagingBytes = GOL_STAGING_BYTES;
+static_assert(kStagingBytes % 16 == 0 && kStagingBytes >= 4096,
+              "staging chunks keep k_pack's 16-byte loads aligned and hold a few rows");
 
 }  // namespace
 
@@ -101,7 +116,7 @@ struct gol_ctx {
     bool blocked_pending = false;
     long long nonbinary = 0;
     std::vector<uint8_t> raw_turn0;          // loaded bytes, kept only while non-binary & turn == 0
-    unsigned long long *counts = nullptr;    // (kRing + 1) * kShards
+    unsigned long long *counts = nullptr;    // (kRingSlots + 1) * kShards
     unsigned long long *h_counts = nullptr;  // pinned mirror of one slot
     uint8_t *staging = nullptr;
     size_t staging_size = 0;
@@ -472,7 +487,7 @@ bool stepping_il(const gol_ctx *c, int k)
 // popcount of owned rows of the current board -> *alive (synchronous)
 int count_now(gol_ctx *c, long long *alive)
 {
-    unsigned long long *slot = c->counts + (size_t)kRing * kShards;
+    unsigned long long *slot = c->counts + (size_t)kRingSlots * kShards;
     HIP_OR_FAIL(c, hipMemsetAsync(slot, 0, kShards * sizeof(unsigned long long), c->stream));
     HIP_OR_FAIL(c, golk::launch_popcount(c->board[c->cur], c->nw, c->pitch, own_lo(c), own_hi(c),
                                          slot, c->stream));
@@ -1840,7 +1855,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     hipError_t e;
     if ((e = hipMalloc(&c->board[0], words * 8)) != hipSuccess ||
         (e = hipMalloc(&c->board[1], words * 8)) != hipSuccess ||
-        (e = hipMalloc(&c->counts, (size_t)(kRing + 1) * kShards * 8)) != hipSuccess ||
+        (e = hipMalloc(&c->counts, (size_t)(kRingSlots + 1) * kShards * 8)) != hipSuccess ||
         (e = hipHostMalloc(&c->h_counts, kShards * 8, hipHostMallocDefault)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking)) != hipSuccess ||
@@ -2002,7 +2017,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     }
     if ((e = hipMemsetAsync(c->board[0], 0, words * 8, c->stream)) != hipSuccess ||
         (e = hipMemsetAsync(c->board[1], 0, words * 8, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->counts, 0, (size_t)(kRing + 1) * kShards * 8, c->stream)) !=
+        (e = hipMemsetAsync(c->counts, 0, (size_t)(kRingSlots + 1) * kShards * 8, c->stream)) !=
             hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
         return bail(GOL_EHIP);
@@ -2107,7 +2122,7 @@ int gol_load(gol_ctx *c, const uint8_t *bytes)
     release_blocked(c);
     const size_t words = (size_t)c->buf_rows * c->pitch;
     HIP_OR_FAIL(c, hipMalloc(&c->blocked, words * 8));
-    unsigned long long *nb = c->counts + (size_t)kRing * kShards;
+    unsigned long long *nb = c->counts + (size_t)kRingSlots * kShards;
     HIP_OR_FAIL(c, hipMemsetAsync(nb, 0, kShards * 8, c->stream));
     uint64_t *dst = c->board[0];
     for (int r0 = 0; r0 < c->buf_rows; r0 += chunk_rows) {
@@ -2147,6 +2162,16 @@ int gol_load_packed(gol_ctx *c, const uint64_t *words)
     if (!c || !words) return GOL_EINVAL;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceGuard g(c->device);
+    // the bits past `width` in a row's last word must be 0: the stencil shifts them in as the
+    // east neighbour of cell width - 1, and the counts and the alive list would include them
+    if (const int nb = c->cfg.width & 63) {
+        const uint64_t pad = ~0ull << nb;
+        for (int r = 0; r < c->buf_rows; ++r)
+            if (words[(size_t)r * c->nw + c->nw - 1] & pad)
+                return fail(c, GOL_EINVAL,
+                            "gol_load_packed: buffer row %d has bits set past width %d in its "
+                            "last word (the board is unchanged)", r, c->cfg.width);
+    }
     release_blocked(c);
     HIP_OR_FAIL(c, hipMemcpy2DAsync(c->board[0], (size_t)c->pitch * 8, words, (size_t)c->nw * 8,
                                     (size_t)c->nw * 8, c->buf_rows, hipMemcpyHostToDevice,
@@ -2431,11 +2456,14 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             a.counts = nullptr;
             if (cnt) {
                 const long long next_turn = c->turn + 1;
-                const size_t slot = (size_t)(next_turn % kRing);
-                if (slot == 0 || t == 0) {
-                    // zero the slots of the next min(turns - t, kRing - slot) turns
+                const size_t slot = (size_t)(next_turn % kRingSlots);
+                const size_t in_batch = slot % kRingAhead;
+                if (in_batch == 0 || t == 0) {
+                    // zero the slots of the coming turns up to the next multiple of kRingAhead:
+                    // one memset per kRingAhead turns, and never a slot whose turn
+                    // gol_turn_counts still accepts (see kRingAhead)
                     const size_t nslots =
-                        (size_t)std::min<int64_t>(turns - t, (int64_t)(kRing - slot));
+                        (size_t)std::min<int64_t>(turns - t, (int64_t)(kRingAhead - in_batch));
                     HIP_OR_FAIL(c, hipMemsetAsync(c->counts + slot * kShards, 0,
                                                   nslots * kShards * 8, c->stream));
                 }
@@ -2607,12 +2635,12 @@ int gol_turn_counts(gol_ctx *c, int64_t first_turn, int64_t n, int64_t *out)
             return fail(c, GOL_EINVAL, "turns %lld..%lld not in the recorded window",
                         (long long)first_turn, (long long)(first_turn + n - 1));
         DeviceGuard g(c->device);
-        std::vector<unsigned long long> h((size_t)kRing * kShards);
+        std::vector<unsigned long long> h((size_t)kRingSlots * kShards);
         HIP_OR_FAIL(c, hipMemcpyAsync(h.data(), c->counts, h.size() * 8, hipMemcpyDeviceToHost,
                                       c->stream));
         if (int rc = sync_checked(c)) return rc;
         for (int64_t i = 0; i < n; ++i) {
-            const size_t slot = (size_t)((first_turn + i) % kRing);
+            const size_t slot = (size_t)((first_turn + i) % kRingSlots);
             unsigned long long s = 0;
             for (int k = 0; k < kShards; k++) s += h[slot * kShards + k];
             out[i] = (int64_t)s;

@@ -141,7 +141,13 @@ int gol_fill_random(gol_ctx *ctx, uint64_t seed);
  * words_per_row, for checkers that work on packed boards.  Packed words crossing
  * the ABI (here, gol_read_packed and the halo rows of gol_export_halo /
  * gol_import_halo) are always in the standard layout (cell x = bit x % 64 of word
- * x / 64), whatever internal layout the temporal-blocking kernel runs on. */
+ * x / 64), whatever internal layout the temporal-blocking kernel runs on.
+ * Padding rule: when width % 64 != 0, the bits past `width` in the last word of every row
+ * must be 0 (the stencil reads them as neighbours, and the counts and the alive list would
+ * include them).  gol_load_packed checks every buffer row on the host before it copies:
+ * a set padding bit returns GOL_EINVAL, gol_last_error names the row, and the engine's
+ * board and turn stay as they were.  gol_read_packed and gol_export_halo always write
+ * zero padding. */
 int gol_load_packed(gol_ctx *ctx, const uint64_t *words);
 
 /* Advance `turns` turns.  Torus engine: any turns >= 0.  Strip engine:
@@ -206,7 +212,9 @@ int gol_step_overlap(gol_ctx *ctx, int64_t turns, void *recv_stream);
 /* Consistent (turn, alive) pair of the current board (owned rows only). */
 int gol_snapshot(gol_ctx *ctx, int64_t *turn, int64_t *alive);
 /* Per-turn alive counts recorded by GOL_FLAG_COUNT_EVERY_TURN for turns
- * first_turn .. first_turn+n-1 (must be among the last 4096 turns). */
+ * first_turn .. first_turn+n-1 (must be among the last 4096 turns: turn-4095 .. turn, else
+ * GOL_EINVAL).  Every turn it accepts has its true count, also when called from another thread
+ * during a gol_step or after one that GOL_CONTROL_STOP ended early. */
 int gol_turn_counts(gol_ctx *ctx, int64_t first_turn, int64_t n, int64_t *out);
 
 /* Owned rows as bytes (rows x width, 0/255; at turn 0 the loaded bytes as-is,
@@ -227,7 +235,9 @@ int gol_alive_cells(gol_ctx *ctx, int64_t *xy, int64_t cap, int64_t *n);
  * rows (packed, halo x words_per_row uint64 each) to device buffers `top` and
  * `bottom` on `hip_stream` (NULL = engine stream).  import: copy the neighbour
  * rows into this engine's halos (top = the rows above, from rank r-1's bottom;
- * bottom = the rows below, from rank r+1's top) and reset halo_valid to halo. */
+ * bottom = the rows below, from rank r+1's top) and reset halo_valid to halo.  The imported
+ * rows obey gol_load_packed's padding rule (bits past `width` are 0); they are device memory,
+ * so the engine cannot check them: rows written by gol_export_halo always comply. */
 int gol_export_halo(gol_ctx *ctx, void *top, void *bottom, void *hip_stream);
 int gol_import_halo(gol_ctx *ctx, const void *top, const void *bottom, void *hip_stream);
 /* In-process exchange between two strip engines (any devices, peer copies):

@@ -42,7 +42,7 @@ def _check_libraries_match_sources():
     want = _tree_source_id()
     assert N.lib().gol_source_id().decode() == want, "libgolamd.so is stale: rebuild (make -C csrc)"
     build = os.path.dirname(N.LIB_PATH)
-    for extra in ("libgolamd_spin0.so",):
+    for extra in ("libgolamd_spin0.so", "libgolamd_stage64k.so"):
         p = os.path.join(build, extra)
         if os.path.exists(p):
             # (in a child: two copies of the library in one process would share nothing, but

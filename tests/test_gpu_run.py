@@ -314,6 +314,36 @@ def test_baseline_configs_through_run(gol, workdir, oracle, key, ngpus):
     board = G.parse_pgm(out)
     words, _, nb = oracle.pack(board)
     assert nb == 0 and hashlib.sha256(words.tobytes()).hexdigest() == d["sha256"]
+    if w == 5120:
+        # the list's content, not only its length (5120 wide = 80 words: k_alive_scatter's
+        # second pass over a row): the set of (X, Y) against the oracle's list of the final
+        # board just pinned to the digest.  (16384^2: the list is gigabytes as Cells.)
+        got = np.array([(c.X, c.Y) for c in final[0].Alive], dtype=np.int64).reshape(-1, 2)
+        want = oracle.ref_alive_cells(board)
+        assert got.shape == want.shape
+        order = np.lexsort((got[:, 0], got[:, 1]))
+        assert np.array_equal(got[order], want)
+
+
+@pytest.mark.parametrize("ngpus", [1, 3])
+@pytest.mark.parametrize("w,h", [(96, 40), (40, 96)])
+def test_non_square_run(gol, workdir, oracle, w, h, ngpus):
+    """gol.Run on boards that are not square (wide and tall), on one engine and on 3 strips:
+    the output PGM and FinalTurnComplete.Alive are the numpy oracle's board after 17 turns."""
+    turns = 17
+    _write_random_pgm(workdir, oracle, 11, w, h)
+    start = oracle.unpack(oracle.gen_random(11, w, h), w)
+    want = oracle.np_run(start, turns)
+    p = gol.Params(Turns=turns, Threads=4, ImageWidth=w, ImageHeight=h)
+    kw = dict(ngpus=ngpus, devices=[0] * ngpus) if ngpus > 1 else {}
+    evs = run_collect(gol, p, workdir, **kw)
+    final = [e for e in evs if isinstance(e, gol.FinalTurnComplete)]
+    assert len(final) == 1 and final[0].CompletedTurns == turns
+    ys, xs = np.nonzero(want == 255)
+    assert len(final[0].Alive) == len(xs)
+    assert set((c.X, c.Y) for c in final[0].Alive) == set(zip(xs.tolist(), ys.tolist()))
+    out = (workdir / "out" / f"{w}x{h}x{turns}.pgm").read_bytes()
+    assert out == f"P5\n{w} {h}\n255\n".encode() + want.tobytes()
 
 
 # --------------------------------------- the INTEGRATION.md cgo stub, run as a C program

@@ -175,3 +175,38 @@ def test_config_alive_series_prefix(oracle):
     s = G.config_alive_series(5120, 5120, 1)
     _, counts = oracle.bit_run(oracle.gen_random(1, 5120, 5120), 5120, 20, counts=True)
     assert [s[t] for t in range(1, 21)] == [int(c) for c in counts]
+
+
+@pytest.mark.parametrize("w,h", [(2, 1), (63, 3), (64, 5), (65, 33), (80, 3), (100, 33),
+                                 (208, 5), (4096, 3), (4112, 5), (4160, 33), (8320, 5)])
+def test_structured_boards_alive_list_and_pack(oracle, w, h):
+    """The reference side of tests/test_gpu_io.py, proven here: on every structured board
+    (io_boards.MAKERS) the plain numpy alive list (np.argwhere, row-major {x, y}) is
+    oracle.ref_alive_cells, oracle.pack puts cell x at bit x % 64 of word x // 64 with zero
+    padding and unpacks to the same bytes, popcount is the byte count, and one turn of the bit
+    oracle is one np.roll turn."""
+    import io_boards as B
+    for name, make in B.MAKERS.items():
+        b = make(w, h)
+        assert b.shape == (h, w) and b.dtype == np.uint8 and set(np.unique(b)) <= {0, 255}
+        cells = B.np_alive_cells(b)
+        assert np.array_equal(cells, oracle.ref_alive_cells(b)), name
+        assert np.array_equal(B.np_alive_cells(b, 7), oracle.ref_alive_cells(b) + [0, 7]), name
+        words, blk, nb = oracle.pack(b)
+        assert nb == 0 and not blk.any()
+        bits = np.zeros((h, words.shape[1] * 64), dtype=np.uint8)
+        bits[:, :w] = b == 255
+        want = np.packbits(bits, axis=1, bitorder="little").view("<u8")
+        assert np.array_equal(words, want.astype(np.uint64)), name
+        assert np.array_equal(oracle.unpack(words, w), b), name
+        assert oracle.popcount(words, w) == len(cells) == oracle.ref_alive_count(b), name
+        assert np.array_equal(oracle.unpack(oracle.bit_run(words, w, 1), w), oracle.np_step(b)), name
+    nbz = B.nonbinary_board(130, 33)
+    assert np.array_equal(B.np_alive_cells(nbz), oracle.ref_alive_cells(nbz))
+    # the boards are what their names say
+    assert B.MAKERS["full"](w, h).all() and not B.MAKERS["empty"](w, h).any()
+    assert B.np_alive_cells(B.MAKERS["first_cell"](w, h)).tolist() == [[0, 0]]
+    assert B.np_alive_cells(B.MAKERS["last_cell"](w, h)).tolist() == [[w - 1, h - 1]]
+    assert B.np_alive_cells(B.MAKERS["last_bit"](w, h)).tolist() == [[w - 1, y] for y in range(h)]
+    assert (B.MAKERS["alt_rows"](w, h).sum(axis=1) // 255).tolist() == [w * (1 - y % 2) for y in range(h)]
+    assert abs(float((B.MAKERS["random16"](w, 64) == 255).mean()) - 1 / 16) < 0.05
