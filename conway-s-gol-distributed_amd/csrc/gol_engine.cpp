@@ -120,6 +120,12 @@ struct gol_ctx {
     unsigned long long *h_counts = nullptr;  // pinned mirror of one slot
     uint8_t *staging = nullptr;
     size_t staging_size = 0;
+    // gol_flipped_cells: board[cur ^ 1] holds the board exactly one turn back, both halves in
+    // the standard layout (the last step ran one turn and nothing has written the other half
+    // or flipped `cur` since)
+    bool prev_valid = false;
+    long long *flip_rows = nullptr;          // rows counts + (rows + 1) offsets (first call on)
+    long long *h_flip_total = nullptr;       // pinned: the list length
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;              // boundary-band launches of gol_step_overlap
@@ -377,6 +383,7 @@ int ensure_layout(gol_ctx *c, bool il)
                                            c->pitch, c->buf_rows, c->nw, il, c->stream));
     c->cur ^= 1;
     c->il = il;
+    c->prev_valid = false;                   // the conversion overwrote the previous board
     return GOL_OK;
 }
 
@@ -2021,6 +2028,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
             hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
         return bail(GOL_EHIP);
+    c->prev_valid = false;                   // (the timing launches above stepped the buffers)
     *out = c;
     return GOL_OK;
 }
@@ -2050,6 +2058,8 @@ void gol_destroy(gol_ctx *c)
         if (c->blocked) (void)hipFree(c->blocked);
         if (c->counts) (void)hipFree(c->counts);
         if (c->staging) (void)hipFree(c->staging);
+        if (c->flip_rows) (void)hipFree(c->flip_rows);
+        if (c->h_flip_total) (void)hipHostFree(c->h_flip_total);
         if (c->h_counts) (void)hipHostFree(c->h_counts);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
         if (c->side) (void)hipStreamDestroy(c->side);
@@ -2120,6 +2130,7 @@ int gol_load(gol_ctx *c, const uint8_t *bytes)
     int rc = ensure_staging(c, (size_t)chunk_rows * row_bytes);
     if (rc) return rc;
     release_blocked(c);
+    c->prev_valid = false;                   // (the first chunk may overwrite board[cur ^ 1])
     const size_t words = (size_t)c->buf_rows * c->pitch;
     HIP_OR_FAIL(c, hipMalloc(&c->blocked, words * 8));
     unsigned long long *nb = c->counts + (size_t)kRingSlots * kShards;
@@ -2173,6 +2184,7 @@ int gol_load_packed(gol_ctx *c, const uint64_t *words)
                             "last word (the board is unchanged)", r, c->cfg.width);
     }
     release_blocked(c);
+    c->prev_valid = false;
     HIP_OR_FAIL(c, hipMemcpy2DAsync(c->board[0], (size_t)c->pitch * 8, words, (size_t)c->nw * 8,
                                     (size_t)c->nw * 8, c->buf_rows, hipMemcpyHostToDevice,
                                     c->stream));
@@ -2195,6 +2207,7 @@ int gol_fill_random(gol_ctx *c, uint64_t seed)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceGuard g(c->device);
     release_blocked(c);
+    c->prev_valid = false;
     const long long grow0 = (long long)c->cfg.row_offset - c->cfg.halo;
     HIP_OR_FAIL(c, golk::launch_fill_random(c->board[0], c->cfg.width, c->nw, c->pitch,
                                             c->buf_rows, grow0, c->cfg.height, seed, c->stream));
@@ -2476,6 +2489,10 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
         }
         c->cur ^= 1;
+        // a step of exactly one turn leaves the board one turn back in the other half, both in
+        // the standard layout; a longer step never does for its caller, however it was cut
+        // into launches (a board without multi-turn kernels runs it as one-turn launches)
+        c->prev_valid = k == 1 && turns == 1;
         c->turn += k;
         c->progress.store(c->turn);
         c->launches += 1;
@@ -2772,6 +2789,84 @@ int gol_alive_cells(gol_ctx *c, int64_t *xy, int64_t cap, int64_t *n)
             r0 = r1;
         }
         return done(GOL_OK);
+    });
+}
+
+int gol_flipped_cells(gol_ctx *c, int64_t *xy, int64_t cap, int64_t *n)
+{
+    if (!c || !n || cap < 0 || (cap > 0 && !xy)) return GOL_EINVAL;
+    return run_read(c, [&]() -> int {
+        if (!c->prev_valid || c->il)
+            return fail(c, GOL_ESTATE,
+                        "gol_flipped_cells: the previous board is not held (valid after a "
+                        "one-turn gol_step, until the next load, longer step or layout change)");
+        DeviceGuard g(c->device);
+        const int rows = c->cfg.rows;
+        if (!c->flip_rows) {                 // scratch for the engine's lifetime
+            HIP_OR_FAIL(c, hipMalloc((void **)&c->flip_rows, ((size_t)rows * 2 + 1) * 8));
+            HIP_OR_FAIL(c, hipHostMalloc((void **)&c->h_flip_total, 8, hipHostMallocDefault));
+        }
+        long long *d_rc = c->flip_rows, *d_off = c->flip_rows + rows;
+        const uint64_t *cur = c->board[c->cur], *prev = c->board[c->cur ^ 1];
+        const long long per_cell = 16;
+        HIP_OR_FAIL(c, golk::launch_flip_offsets(cur, prev, c->nw, c->pitch, own_lo(c), rows, d_rc,
+                                                 d_off, c->stream));
+        HIP_OR_FAIL(c, hipMemcpyAsync(c->h_flip_total, d_off + rows, 8, hipMemcpyDeviceToHost,
+                                      c->stream));
+        if (int rc = sync_checked(c)) return rc;
+        const long long total = *c->h_flip_total;
+        *n = total;
+        if (cap == 0 || total == 0) return GOL_OK;
+        if (total * per_cell <= (long long)kStagingBytes) {
+            // the common case: one scatter, and the host reads nothing but the list.  The
+            // staging buffer grows by doubling, so a run's lists soon stop reallocating it.
+            if (c->staging_size < (size_t)(total * per_cell))
+                if (int rc = ensure_staging(c, std::min<size_t>(kStagingBytes,
+                                                                (size_t)(total * per_cell) * 2)))
+                    return rc;
+            HIP_OR_FAIL(c, golk::launch_flip_scatter(cur, prev, c->nw, c->pitch, own_lo(c), rows,
+                                                     (long long)c->cfg.row_offset, d_off, 0,
+                                                     (long long *)c->staging, c->stream));
+            HIP_OR_FAIL(c, hipMemcpyAsync(xy, c->staging,
+                                          (size_t)std::min<long long>(total, cap) * per_cell,
+                                          hipMemcpyDeviceToHost, c->stream));
+            return sync_checked(c);
+        }
+        // a list larger than the staging budget: row chunks, as gol_alive_cells (the row counts
+        // come to the host to cut the chunks; the device offsets are rebased per chunk)
+        std::vector<long long> rc((size_t)rows), off((size_t)rows);
+        HIP_OR_FAIL(c, hipMemcpyAsync(rc.data(), d_rc, (size_t)rows * 8, hipMemcpyDeviceToHost,
+                                      c->stream));
+        if (int rc2 = sync_checked(c)) return rc2;
+        long long sum = 0;
+        for (int r = 0; r < rows; r++) {
+            off[(size_t)r] = sum;
+            sum += rc[(size_t)r];
+        }
+        long long r0 = 0;
+        while (r0 < rows && off[(size_t)r0] < cap) {
+            long long r1 = r0;
+            while (r1 < rows && (off[(size_t)r1] + rc[(size_t)r1] - off[(size_t)r0]) * per_cell <=
+                                    (long long)kStagingBytes)
+                ++r1;
+            if (r1 == r0) r1 = r0 + 1;  // a single row larger than the budget
+            const long long cells = off[(size_t)r1 - 1] + rc[(size_t)r1 - 1] - off[(size_t)r0];
+            if (int rc2 = ensure_staging(c, (size_t)std::max<long long>(cells * per_cell, 16)))
+                return rc2;
+            HIP_OR_FAIL(c, golk::launch_flip_scatter(cur, prev, c->nw, c->pitch,
+                                                     own_lo(c) + (int)r0, (int)(r1 - r0),
+                                                     (long long)c->cfg.row_offset + r0, d_off + r0,
+                                                     off[(size_t)r0], (long long *)c->staging,
+                                                     c->stream));
+            const long long want = std::min<long long>(cells, cap - off[(size_t)r0]);
+            if (want > 0)
+                HIP_OR_FAIL(c, hipMemcpyAsync(xy + 2 * off[(size_t)r0], c->staging,
+                                              (size_t)want * per_cell, hipMemcpyDeviceToHost,
+                                              c->stream));
+            if (int rc2 = sync_checked(c)) return rc2;
+            r0 = r1;
+        }
+        return GOL_OK;
     });
 }
 

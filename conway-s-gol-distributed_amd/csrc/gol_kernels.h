@@ -289,4 +289,16 @@ hipError_t launch_alive_scatter(const uint64_t *w, int nw, int pitch, int row0, 
                                 long long grow0, const long long *row_offsets,
                                 long long *xy, hipStream_t s);
 
+// Flip list (cells that differ between two boards of one pitch, rows [row0, row0 + nrows)):
+// per-row popcounts of cur ^ prev into row_counts[nrows], their exclusive scan into
+// row_offsets[nrows + 1] (the last entry is the total) -- all on the device -- then a
+// row-major scatter of {x, y} int64 pairs to xy[row_offsets[r] - rebase ...].
+hipError_t launch_flip_offsets(const uint64_t *cur, const uint64_t *prev, int nw, int pitch,
+                               int row0, int nrows, long long *row_counts,
+                               long long *row_offsets, hipStream_t s);
+hipError_t launch_flip_scatter(const uint64_t *cur, const uint64_t *prev, int nw, int pitch,
+                               int row0, int nrows, long long grow0,
+                               const long long *row_offsets, long long rebase, long long *xy,
+                               hipStream_t s);
+
 }  // namespace golk

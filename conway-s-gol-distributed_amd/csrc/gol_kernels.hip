@@ -28,6 +28,8 @@
 // K3 k_row_popcount + k_alive_scatter — FinalTurnComplete's row-major alive
 //   list (Local/gol/distributor.go:229-239) by stream compaction.
 // K4 k_pack / k_unpack — PGM bytes <-> bits, with the non-binary mask.
+// K5 k_row_flipcount + k_row_scan + k_flip_scatter — CellFlipped's per-turn flip list
+//   (Local/gol/event.go:47-57): K3's compaction on cur ^ prev, offsets scanned on the device.
 #include "gol_device.h"
 
 #include <type_traits>
@@ -489,21 +491,19 @@ __global__ __launch_bounds__(256) void k_row_popcount(const uint64_t *__restrict
     if (lane == 0) row_counts[r] = (long long)acc;
 }
 
-__global__ __launch_bounds__(256) void k_alive_scatter(const uint64_t *__restrict__ w, int nw,
-                                                       int pitch, int row0, int nrows,
-                                                       long long grow0,
-                                                       const long long *__restrict__ row_off,
-                                                       long long *__restrict__ xy)
+// One wavefront writes the {x, y} pairs of one row's set bits (XOR: of row[j] ^ other[j]) in
+// x order from list position `base` on (K3's and K5's scatter).
+template <bool XOR>
+__device__ __forceinline__ void scatter_row(const uint64_t *__restrict__ row,
+                                            const uint64_t *__restrict__ other, int nw,
+                                            long long base, long long y,
+                                            long long *__restrict__ xy)
 {
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= nrows) return;
-    const uint64_t *row = w + (size_t)(row0 + r) * pitch;
-    long long base = row_off[r];
-    const long long y = grow0 + r;
     for (int j0 = 0; j0 < nw; j0 += 64) {
         const int j = j0 + lane;
         uint64_t v = j < nw ? row[j] : 0ull;
+        if (XOR) v ^= j < nw ? other[j] : 0ull;
         const int c = __builtin_popcountll(v);
         // inclusive scan of c across the wavefront
         int incl = c;
@@ -522,6 +522,92 @@ __global__ __launch_bounds__(256) void k_alive_scatter(const uint64_t *__restric
         }
         base += __shfl(incl, 63, 64);
     }
+}
+
+__global__ __launch_bounds__(256) void k_alive_scatter(const uint64_t *__restrict__ w, int nw,
+                                                       int pitch, int row0, int nrows,
+                                                       long long grow0,
+                                                       const long long *__restrict__ row_off,
+                                                       long long *__restrict__ xy)
+{
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const uint64_t *row = w + (size_t)(row0 + r) * pitch;
+    scatter_row<false>(row, nullptr, nw, row_off[r], grow0 + r, xy);
+}
+
+// ------------------------------------------------------- K5: flip lists
+// CellFlipped (Local/gol/event.go:47-57): the cells that differ between two boards of one
+// pitch -- the two halves of the engine's double buffer after a one-turn launch -- as K3's
+// row-major {x, y} list of cur ^ prev.  Padding bits are 0 in both boards, so none is set in
+// the XOR.  One wavefront per row.
+__global__ __launch_bounds__(256) void k_row_flipcount(const uint64_t *__restrict__ cur,
+                                                       const uint64_t *__restrict__ prev, int nw,
+                                                       int pitch, int row0, int nrows,
+                                                       long long *__restrict__ row_counts)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const uint64_t *a = cur + (size_t)(row0 + r) * pitch;
+    const uint64_t *b = prev + (size_t)(row0 + r) * pitch;
+    unsigned long long acc = 0;
+    for (int j = lane; j < nw; j += 64) acc += __builtin_popcountll(a[j] ^ b[j]);
+    acc = wave_sum(acc);
+    if (lane == 0) row_counts[r] = (long long)acc;
+}
+
+// Exclusive scan of the row counts: row_off[r] = counts[0] + .. + counts[r - 1], and the total
+// in row_off[nrows].  One workgroup of kScanThreads walks the rows in slices of its size, so
+// the host never sees a per-row number.
+constexpr int kScanThreads = 1024;
+__global__ __launch_bounds__(kScanThreads) void k_row_scan(const long long *__restrict__ counts,
+                                                           int nrows,
+                                                           long long *__restrict__ row_off)
+{
+    __shared__ long long part[kScanThreads / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long carry = 0;                                   // rows before this slice (uniform)
+    for (int r0 = 0; r0 < nrows; r0 += kScanThreads) {
+        const int r = r0 + (int)threadIdx.x;
+        const long long c = r < nrows ? counts[r] : 0;
+        long long incl = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) part[wv] = incl;
+        __syncthreads();
+        long long before = 0, slice = 0;
+#pragma unroll
+        for (int i = 0; i < kScanThreads / 64; ++i) {
+            const long long p = part[i];
+            before += i < wv ? p : 0;
+            slice += p;
+        }
+        if (r < nrows) row_off[r] = carry + before + incl - c;
+        carry += slice;
+        __syncthreads();                                   // part[] is rewritten by the next slice
+    }
+    if (threadIdx.x == 0) row_off[nrows] = carry;
+}
+
+// `rebase` is subtracted from every row offset: a chunk of rows scatters into a list that
+// starts at its own first cell.
+__global__ __launch_bounds__(256) void k_flip_scatter(const uint64_t *__restrict__ cur,
+                                                      const uint64_t *__restrict__ prev, int nw,
+                                                      int pitch, int row0, int nrows,
+                                                      long long grow0,
+                                                      const long long *__restrict__ row_off,
+                                                      long long rebase,
+                                                      long long *__restrict__ xy)
+{
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= nrows) return;
+    const uint64_t *a = cur + (size_t)(row0 + r) * pitch;
+    const uint64_t *b = prev + (size_t)(row0 + r) * pitch;
+    scatter_row<true>(a, b, nw, row_off[r] - rebase, grow0 + r, xy);
 }
 
 // ------------------------------------------------------------- launchers
@@ -856,6 +942,31 @@ hipError_t launch_alive_scatter(const uint64_t *w, int nw, int pitch, int row0, 
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_alive_scatter, dim3(blocks), dim3(256), 0, s, w, nw, pitch, row0,
                        nrows, grow0, row_offsets, xy);
+    return hipGetLastError();
+}
+
+hipError_t launch_flip_offsets(const uint64_t *cur, const uint64_t *prev, int nw, int pitch,
+                               int row0, int nrows, long long *row_counts,
+                               long long *row_offsets, hipStream_t s)
+{
+    const int blocks = (nrows + 3) / 4;
+    if (blocks > 0)
+        hipLaunchKernelGGL(k_row_flipcount, dim3(blocks), dim3(256), 0, s, cur, prev, nw, pitch,
+                           row0, nrows, row_counts);
+    hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(kScanThreads), 0, s, row_counts, nrows,
+                       row_offsets);
+    return hipGetLastError();
+}
+
+hipError_t launch_flip_scatter(const uint64_t *cur, const uint64_t *prev, int nw, int pitch,
+                               int row0, int nrows, long long grow0,
+                               const long long *row_offsets, long long rebase, long long *xy,
+                               hipStream_t s)
+{
+    const int blocks = (nrows + 3) / 4;
+    if (blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_flip_scatter, dim3(blocks), dim3(256), 0, s, cur, prev, nw, pitch, row0,
+                       nrows, grow0, row_offsets, rebase, xy);
     return hipGetLastError();
 }
 

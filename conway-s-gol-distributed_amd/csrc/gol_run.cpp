@@ -462,6 +462,35 @@ struct Strips {
         }
         return GOL_OK;
     }
+
+    // the cells that flipped in the last turn (every engine's last launch ran one turn): the
+    // engines' lists in strip order, which is row-major over the whole board
+    int flipped_cells(std::vector<int64_t> &xy)
+    {
+        xy.clear();
+        for (auto *e : eng) {
+            int64_t n = 0;
+            int rc = gol_flipped_cells(e, nullptr, 0, &n);
+            if (rc) return fail_from(e, rc);
+            const size_t base = xy.size();
+            xy.resize(base + (size_t)n * 2);
+            if (n) {
+                rc = gol_flipped_cells(e, xy.data() + base, n, &n);
+                if (rc) return fail_from(e, rc);
+            }
+        }
+        return GOL_OK;
+    }
+
+    long long nonbinary_cells()
+    {
+        long long s = 0;
+        for (auto *e : eng) {
+            gol_info info;
+            if (gol_get_info(e, &info) == GOL_OK) s += info.nonbinary_cells;
+        }
+        return s;
+    }
 };
 
 }  // namespace
@@ -556,11 +585,17 @@ void gol_run::run()
         return send(e);
     };
 
-    HostBuf prev;                                     // CellFlipped: previous board
-    if (emit_cell_flipped) {
+    // CellFlipped: each turn's flips come from the engines (gol_flipped_cells: the XOR of the
+    // two halves of the double buffer).  Only the first turn of a run whose image has
+    // non-binary bytes, or that resumes (the events start from the image, the board from the
+    // retained one), is compared on the host against the image bytes.
+    HostBuf prev;
+    bool host_flips = emit_cell_flipped && (cont || st.nonbinary_cells() > 0);
+    if (host_flips) {
         if (!prev.alloc((size_t)W * H)) return die("out of host memory");
         std::memcpy(prev.data(), pix, (size_t)W * H);
     }
+    std::vector<int64_t> flips;
     pix = nullptr;
     file.release();
 
@@ -693,11 +728,11 @@ void gol_run::run()
             else if (ms > 4.0 && chunk > 1) chunk /= 2;
             continue;
         }
-        if (st.sync()) return die(st.err);
-        {
+        // with CellFlipped on, chunks are single turns so every flip is reported
+        if (host_flips) {
+            if (st.sync()) return die(st.err);
             HostBuf cur;
             if (st.read_board(cur)) return die(st.err);
-            // with CellFlipped on, chunks are single turns so every flip is reported
             for (int y = 0; y < H; y++)
                 for (int x = 0; x < W; x++)
                     if (cur.data()[(size_t)y * W + x] != prev.data()[(size_t)y * W + x]) {
@@ -706,7 +741,20 @@ void gol_run::run()
                         cf.y = y;
                         if (!send(cf)) return close();
                     }
-            std::swap(prev, cur);
+            if (n > 0) {                              // the board has left the image behind
+                host_flips = false;
+                prev.release();
+            } else {
+                std::swap(prev, cur);                 // (a key stopped the step before its turn)
+            }
+        } else if (n > 0) {                           // (n == 0: a key stopped the step)
+            if (st.flipped_cells(flips)) return die(st.err);
+            for (size_t i = 0; i + 1 < flips.size(); i += 2) {
+                gol_event cf = make_ev(GOL_EV_CELL_FLIPPED, turn + 1);
+                cf.x = flips[i];
+                cf.y = flips[i + 1];
+                if (!send(cf)) return close();
+            }
         }
         if (emit_turn_complete)
             for (long long t = 1; t <= n; t++)

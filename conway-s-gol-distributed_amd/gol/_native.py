@@ -135,6 +135,7 @@ SIGNATURES = {
     "gol_get_world": (_i32, [_vp, _u8p, _i64p]),
     "gol_read_packed": (_i32, [_vp, _u64p]),
     "gol_alive_cells": (_i32, [_vp, _i64p, _i64, _i64p]),
+    "gol_flipped_cells": (_i32, [_vp, _i64p, _i64, _i64p]),
     "gol_export_halo": (_i32, [_vp, _vp, _vp, _vp]),
     "gol_import_halo": (_i32, [_vp, _vp, _vp, _vp]),
     "gol_copy_halo_from_upper": (_i32, [_vp, _vp]),

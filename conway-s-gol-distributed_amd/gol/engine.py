@@ -189,6 +189,17 @@ class Engine:
                                             ctypes.byref(n)))
         return out[: n.value]
 
+    def flipped_cells(self) -> np.ndarray:
+        """Row-major (n, 2) int64 {x, y} list of the cells the last turn flipped (CellFlipped,
+        Local/gol/event.go:47-57).  Valid after step(1); GolError(GOL_ESTATE) otherwise."""
+        n = ctypes.c_int64()
+        self._c(self._L.gol_flipped_cells(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros((max(n.value, 1), 2), dtype=np.int64)
+        if n.value:
+            self._c(self._L.gol_flipped_cells(self._h, out.ctypes.data_as(N._i64p), n.value,
+                                              ctypes.byref(n)))
+        return out[: n.value]
+
     # -- strip halo exchange (device pointers)
     def export_halo(self, top_ptr: int, bottom_ptr: int, stream_ptr: int | None = None):
         self._c(self._L.gol_export_halo(self._h, ctypes.c_void_p(top_ptr),

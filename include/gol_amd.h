@@ -31,7 +31,7 @@
  *
  * Threading: one thread drives an engine (gol_step, loads, halo calls).  The read-only
  * calls (gol_snapshot, gol_get_info, gol_read_board, gol_get_world, gol_read_packed,
- * gol_alive_cells, gol_turn_counts) may come from other threads at any time: during a gol_step the stepping
+ * gol_alive_cells, gol_flipped_cells, gol_turn_counts) may come from other threads at any time: during a gol_step the stepping
  * thread serves them at its next launch boundary, on a turn-consistent board; while the
  * step is parked on GOL_CONTROL_PAUSE they run at once (the reference Server's mutex is
  * held only around the per-turn commit: Server/gol/distributor.go:62-75,131-134).  A run
@@ -230,6 +230,19 @@ int gol_read_packed(gol_ctx *ctx, uint64_t *out);
 /* Row-major alive-cell list {x, y} (y = global row) of the owned rows, as
  * int64 pairs; writes min(n, cap) pairs and sets *n to the total. */
 int gol_alive_cells(gol_ctx *ctx, int64_t *xy, int64_t cap, int64_t *n);
+/* CellFlipped (Local/gol/event.go:47-57): the cells of the owned rows whose state differs
+ * between the current board and the board one turn earlier, as row-major {x, y} int64 pairs
+ * (y = global row); writes min(n, cap) pairs and sets *n to the total (cap == 0 or *n == 0:
+ * xy is not touched).  Computed on the device from the two halves of the double buffer, so it
+ * is valid only while the other half still holds the board exactly one turn back: after a
+ * gol_step(ctx, 1) or gol_step_overlap(ctx, 1, ..) (a gol_step of 0 turns changes nothing),
+ * until the next gol_load / gol_load_packed / gol_fill_random, a step of more than one turn, or
+ * a gol_halo_buffers that converts the board to the interleaved layout; halo imports keep it
+ * valid.  Otherwise GOL_ESTATE.  A flip is a change of the packed bit (bit set <=> byte ==
+ * 255): a cell loaded with a byte that is neither 0 nor 255 has bit 0 before the first turn
+ * and is dead after it, so it is not reported on that turn although its byte changed (the run
+ * driver compares that one turn's bytes on the host). */
+int gol_flipped_cells(gol_ctx *ctx, int64_t *xy, int64_t cap, int64_t *n);
 
 /* Strip mode halo exchange.  export: copy the first and the last `halo` owned
  * rows (packed, halo x words_per_row uint64 each) to device buffers `top` and
