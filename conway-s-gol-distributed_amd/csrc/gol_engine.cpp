@@ -2384,6 +2384,13 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             a.row_lo = 0;
             a.row_hi = c->buf_rows;
         }
+        // an overlapped window whose first launch runs on the other word layout (a one-turn
+        // window on an engine of multi-turn launches): the conversion reads the halo rows, so
+        // it follows the caller's receives -- gol_halo_buffers handed out rows of this board
+        if (xstream && t == 0 && c->il != stepping_il(c, k)) {
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_side, xstream));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        }
         if (int rc = ensure_layout(c, stepping_il(c, k))) return rc;
         a.in = c->board[c->cur];
         a.out = c->board[c->cur ^ 1];
