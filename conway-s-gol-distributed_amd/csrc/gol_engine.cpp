@@ -134,6 +134,9 @@ struct gol_ctx {
     long long launches = 0;
     int halo_valid = 0;
     bool blocking_limited = false;           // temporal blocking off: buffer >= 2 GiB
+    // GOL_FLAG_COUNT_EVERY_TURN engines: multi-turn launches with the counts fused into
+    // k_step_tile are allowed (GOL_COUNT_BLOCKING=0 at create: one-turn launches, for A/B)
+    bool count_blocking = false;
     // kMultiWgPg: published boundary rows and per-(tile, stage) flags (uncached, grow-only)
     uint64_t *pg_rows = nullptr;
     unsigned *pg_flags = nullptr;
@@ -447,12 +450,35 @@ int band_for_depth(gol_ctx *c, int k)
 // gol_step and gol_halo_buffers both use this rule (the zero-copy halo layout must be the
 // layout the first launch after an exchange runs on; every planned kernel runs on the
 // interleaved layout).
+// A count engine (GOL_FLAG_COUNT_EVERY_TURN) runs multi-turn launches only on k_step_tile at
+// a code with a counted instantiation (golk::kTileCountCodes); every other count engine -- K1s
+// / K1w kernels, a GOL_TILE code without one, generic widths, blocking_limited,
+// GOL_COUNT_BLOCKING=0 -- runs one-turn launches with the count fused into the stencil.
+bool count_fused(const gol_ctx *c)
+{
+    return (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) && c->count_blocking && c->tpl > 1 &&
+           c->multi_variant == golk::kMultiTile && golk::tile_code_counted(c->tile_seg);
+}
+
 Launch plan_launch(gol_ctx *c, int64_t room)
 {
     Launch L{1, c->multi_variant, c->band, 0, 0};
-    if (c->tpl <= 1 || room < 2 || (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) ||
-        c->blocked_pending)
-        return L;
+    if (c->tpl <= 1 || room < 2 || c->blocked_pending) return L;
+    if (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) {
+        if (!count_fused(c)) return L;
+        // a counted launch adds into K consecutive slots of the count ring: it ends at the
+        // ring's last slot at the latest (once per kRingSlots turns).  No K1p / K1q, no timed
+        // plans (they mix kernels without a counted form): the even split at the tuned depth.
+        room = std::min<int64_t>(room, kRingSlots - (c->turn + 1) % kRingSlots);
+        if (room < 2) return L;
+        const int64_t nl = (room + c->tpl - 1) / c->tpl;
+        const int k = (int)((room + nl - 1) / nl);
+        const int band = band_for_depth(c, k);
+        if (!golk::multi_ok(c->cfg.width, k, c->multi_variant) ||
+            !golk::tile_shape_ok(c->nw, k, band, c->tile_w, c->tile_seg))
+            return L;
+        return Launch{k, c->multi_variant, band, c->tile_w, c->tile_seg};
+    }
     // (another engine on the device could hold CUs the resident tiles need: then plain
     // launches -- a starved wait would give up and report GOL_EHIP, but never hang)
     if (c->persist_k > 0 && !is_strip(c) && room >= 2 * c->persist_k &&
@@ -682,7 +708,8 @@ double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg)
 // (K, TW)), fastest first.  TW: every width that splits a row into ntx near-equal tiles; TH:
 // the tallest tile the workgroup holds (16 waves) and the heights whose tile count fills 1..4
 // resident tiles per CU or a few more tile rows.
-std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep)
+// cnt: for a count engine's fused launches -- codes with a counted instantiation only.
+std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt = false)
 {
     // SEG, and SEG + 100 for the interior-rows-first turn order (gol_tile.hip)
     static constexpr int kSegs[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 40, 48,
@@ -700,6 +727,7 @@ std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep)
             const int C = tw + 2, G = 64 / C;
             const long long ntx = (nw + tw - 1) / tw;
             for (int seg : kSegs) {
+                if (cnt && !golk::tile_code_counted(seg)) continue;
                 const int thmax = golk::kTileMaxWavesHost * G * (seg % 100) - 2 * K;
                 if (thmax < 1) continue;
                 std::vector<long long> ntys;
@@ -760,6 +788,11 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
     *us = 0.f;
     const int nw = c->nw, rows = c->buf_rows;
     if (nw % W) return TileShape{};
+    // a count engine searches the codes with a counted instantiation (one word per lane) and
+    // times the counted kernel: the counts of each launch's turns go to the ring's first slots
+    // (the ring is cleared when the create ends)
+    const bool cnt = (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) && c->count_blocking;
+    if (cnt && W != 1) return TileShape{};
     const int nl = nw / W;                           // lane columns (W words each)
     struct WOpt { double useful; int tw; };
     std::vector<WOpt> wopt;
@@ -784,13 +817,17 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
     static_assert(all_shipped(kSegs1) && all_shipped(kSegs2), "a tile code outside kTileCodes");
     std::vector<int> segs = W == 1 ? std::vector<int>(std::begin(kSegs1), std::end(kSegs1))
                                    : std::vector<int>(std::begin(kSegs2), std::end(kSegs2));
+    if (cnt)
+        segs.erase(std::remove_if(segs.begin(), segs.end(),
+                                  [](int sg) { return !golk::tile_code_counted(sg); }),
+                   segs.end());
     struct P { int K, wv, tw, seg, th = 0; };          // th > 0: this height (<= wv's)
     auto shape = [&](const P &p) -> TileShape {
         const int G = 64 / (p.tw + 2);
         int th = p.wv * G * (p.seg % 100) - 2 * p.K;
         if (p.th > 0) th = std::min(th, p.th);
         th = std::min(th, rows);
-        if (th < std::min(8, rows) ||
+        if (th < std::min(8, rows) || (cnt && !golk::tile_code_counted(p.seg)) ||
             !golk::tile_shape_ok(nw, p.K, th, p.tw, p.seg))
             return TileShape{};
         return TileShape{p.K, th, p.tw, p.seg, 0};
@@ -805,6 +842,9 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
     a.multi_words = 1;
     a.multi_variant = golk::kMultiTile;
     a.err = c->d_err;
+    a.cnt_lo = own_lo(c);
+    a.cnt_hi = own_hi(c);
+    a.counts = cnt ? c->counts : nullptr;
     if (golk::launch_fill_random(c->board[0], c->cfg.width, nw, c->pitch, rows, 0, rows, 12345,
                                  c->stream) != hipSuccess)
         return TileShape{};
@@ -846,7 +886,7 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
                     c->cfg.width, rows, t.K, t.th, t.tw, t.seg, best * 1000.f);
         return best;
     };
-    P cur{kfix > 0 ? kfix : 32, 8, tws.empty() ? 30 : tws[0], W == 1 ? 16 : 1008};
+    P cur{kfix > 0 ? kfix : 32, 8, tws.empty() ? 30 : tws[0], W == 1 ? (cnt ? 516 : 16) : 1008};
     // clock ramp, and the repetitions that make a measurement ~0.5 ms of launches
     {
         TileShape t0 = shape(cur);
@@ -1066,6 +1106,15 @@ constexpr KnownShape kKnownShapes[] = {
     // profiles/r06_strip_sweep.log)
     {16384, 8448, {32, 320, 30, 512, 0}, 1.72f},
 };
+
+// (a count engine of a pinned size keeps the pinned shape: its launches run the counted form)
+constexpr bool known_shapes_counted()
+{
+    for (const KnownShape &k : kKnownShapes)
+        if (!golk::tile_code_counted(k.t.seg)) return false;
+    return true;
+}
+static_assert(known_shapes_counted(), "every kKnownShapes code is in golk::kTileCountCodes");
 
 bool known_shape(const gol_ctx *c, KnownShape *out)
 {
@@ -1296,12 +1345,12 @@ void autotune_small(gol_ctx *c)
 {
     float us1 = 0.f, us2 = 0.f;
     const TileShape t1 = tile_search(c, 0, &us1, 1);
-    const TileShape t2 = tile_search(c, 0, &us2, 2);   // two words per lane
+    const TileShape t2 = tile_search(c, 0, &us2, 2);   // two words per lane (count engines: none)
     const bool two = t2.K && (!t1.K || us2 < us1);
     if (!t1.K && !t2.K) return;
     apply_tile(c, two ? t2 : t1);
     c->tuned_us_per_turn = two ? us2 : us1;
-    persist_tune(c);
+    if (!(c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN)) persist_tune(c);   // (K1p has no counted form)
 }
 
 // Create-time timing sweep of the temporal-blocking kernel, its depth K and its band on
@@ -1319,6 +1368,10 @@ void autotune_multi(gol_ctx *c, bool tune_k, bool tune_variant)
     if (tune_variant)
         vars = {golk::kMultiSkewILW16, golk::kMultiWg, golk::kMultiWgHx, golk::kMultiWgPg,
                 golk::kMultiWgHxS, golk::kMultiWgPgS, golk::kMultiTile};
+    // a count engine's multi-turn launches are k_step_tile's counted form or none: only K1t
+    // candidates are timed (with the counts), and no launch plan mixes other kernels in
+    const bool cnt = (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) != 0;
+    if (cnt && tune_variant && c->count_blocking) vars = {golk::kMultiTile};
     int ncu = 0;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
     struct Cand {
@@ -1379,8 +1432,8 @@ void autotune_multi(gol_ctx *c, bool tune_k, bool tune_variant)
     a.modrows = c->buf_rows;
     a.row_lo = 0;
     a.row_hi = c->buf_rows;
-    a.cnt_lo = 0;
-    a.cnt_hi = 0;
+    a.cnt_lo = own_lo(c);
+    a.cnt_hi = own_hi(c);
     a.variant = c->variant;
     a.multi_words = c->multi_words;
     a.wg_prio = c->wg_prio;
@@ -1397,6 +1450,10 @@ void autotune_multi(gol_ctx *c, bool tune_k, bool tune_variant)
         a.multi_variant = cd.var;
         a.tile_w = cd.tw;
         a.tile_seg = cd.seg;
+        a.counts = cnt && c->count_blocking && cd.var == golk::kMultiTile &&
+                           golk::tile_code_counted(cd.seg)
+                       ? c->counts
+                       : nullptr;
         bool ok = hipEventRecord(e0, c->stream) == hipSuccess;
         for (int rep = 0; rep < reps && ok; ++rep) {
             a.in = c->board[rep & 1];
@@ -1488,7 +1545,7 @@ void autotune_multi(gol_ctx *c, bool tune_k, bool tune_variant)
     // interleaved layout, so launches of different kernels mix freely.
     std::vector<Launch> plan;
     float stream_best = 0.f;
-    if (tune_k && tune_variant && pick_t > 0.f) {
+    if (tune_k && tune_variant && pick_t > 0.f && !cnt) {
         struct Fam {
             int var, K, band, tw, seg;
             float T[golk::kMaxTurnsPerLaunch + 1];
@@ -1840,6 +1897,11 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         c->blocking_limited = true;   // reported in gol_info.blocking_limited
     if (!c->fast || c->blocking_limited) c->tpl = 1;
     c->halo_valid = cfg->halo;
+    if (cfg->flags & GOL_FLAG_COUNT_EVERY_TURN) {
+        const char *v = getenv("GOL_COUNT_BLOCKING");    // 0: one-turn launches (A/B, probes)
+        c->count_blocking = !v || atoi(v) != 0;
+    }
+    const bool cntb = c->count_blocking;
 
     DeviceGuard g(dev);
     (void)hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1892,7 +1954,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         int K = cfg->turns_per_launch > 0 ? std::min(cfg->turns_per_launch, golk::kMaxTileTurns) : 0;
         if (const char *v = getenv("GOL_TURNS_PER_LAUNCH"))
             K = std::max(2, std::min(atoi(v), golk::kMaxTileTurns));
-        std::vector<TileShape> cand = tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20);
+        std::vector<TileShape> cand = tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20, cntb);
         for (const TileShape &t : cand)
             if (K == 0 || t.K == K) {
                 apply_tile(c, t);
@@ -1979,7 +2041,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
                           (cfg->turns_per_launch <= 0 || cfg->turns_per_launch <= 8);
     const TuneKey key{dev, cfg->width, c->buf_rows, cfg->turns_per_launch,
                       (tune_small ? 4 : 0) | (tune_var ? 2 : 0) | (pinned ? 1 : 0) |
-                          (c->multi_variant << 3)};
+                          (c->multi_variant << 3) | (cntb ? 1 << 24 : 0)};
     const char *tc = getenv("GOL_AUTOTUNE_CACHE");
     const bool use_cache = !tc || atoi(tc) != 0;
     bool cached = false;
@@ -2345,6 +2407,7 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             ? &c->seq[turns]
             : nullptr;
     size_t fi = 0;
+    long long zero_hi = c->turn;             // count engines: see the ring zeroing below
     c->last.clear();
     c->last_n = 0;
     for (int64_t t = 0; t < turns;) {
@@ -2365,6 +2428,7 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
                 while ((w = c->control.load()) == GOL_CONTROL_PAUSE)
                     std::this_thread::sleep_for(std::chrono::microseconds(200));
                 lk.lock();
+                zero_hi = c->turn;           // (the engine was released: zero again from here)
                 set_stepping(c, true);
                 c->parked.store(false);
             }
@@ -2410,9 +2474,31 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             HIP_OR_FAIL(c, hipEventRecord(c->ev_side, xstream));
             HIP_OR_FAIL(c, hipStreamWaitEvent(c->side, c->ev_side, 0));
         }
+        if (cnt) {
+            // Zero the count slots of this launch's turns c->turn + 1 .. c->turn + k (zero_hi:
+            // the last turn whose slot this step has zeroed).  One memset clears from the first
+            // slot not yet zeroed to the end of its batch of kRingAhead slots (a batch never
+            // wraps the ring), but no further than the step's last turn and never past turn
+            // c->turn + kRingAhead: the slots up to there hold turns <= c->turn - kRing, which
+            // gol_turn_counts no longer accepts, now or at any later launch boundary.  A launch
+            // that straddles a batch boundary takes a second memset (k <= kRingAhead).
+            zero_hi = std::max(zero_hi, c->turn);
+            while (zero_hi < c->turn + k) {
+                const long long z = zero_hi + 1;
+                const size_t slot = (size_t)(z % kRingSlots);
+                const long long e = std::min({z + (long long)(kRingAhead - slot % kRingAhead) - 1,
+                                              c->turn + (long long)kRingAhead,
+                                              c->turn + (long long)(turns - t)});
+                HIP_OR_FAIL(c, hipMemsetAsync(c->counts + slot * kShards, 0,
+                                              (size_t)(e - z + 1) * kShards * 8, c->stream));
+                zero_hi = e;
+            }
+        }
         if (k > 1) {
             a.blocked = nullptr;
-            a.counts = nullptr;
+            // (a count engine's multi-turn launch: k_step_tile_cnt, k consecutive slots --
+            // plan_launch stops at the ring's end)
+            a.counts = cnt ? c->counts + (size_t)((c->turn + 1) % kRingSlots) * kShards : nullptr;
             a.band = plan.band;
             a.multi_variant = plan.var;
             if (plan.var == golk::kMultiTile || plan.var == golk::kMultiTilePersist ||
@@ -2473,22 +2559,7 @@ int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             }
         } else {
             a.blocked = c->blocked_pending ? c->blocked : nullptr;
-            a.counts = nullptr;
-            if (cnt) {
-                const long long next_turn = c->turn + 1;
-                const size_t slot = (size_t)(next_turn % kRingSlots);
-                const size_t in_batch = slot % kRingAhead;
-                if (in_batch == 0 || t == 0) {
-                    // zero the slots of the coming turns up to the next multiple of kRingAhead:
-                    // one memset per kRingAhead turns, and never a slot whose turn
-                    // gol_turn_counts still accepts (see kRingAhead)
-                    const size_t nslots =
-                        (size_t)std::min<int64_t>(turns - t, (int64_t)(kRingAhead - in_batch));
-                    HIP_OR_FAIL(c, hipMemsetAsync(c->counts + slot * kShards, 0,
-                                                  nslots * kShards * 8, c->stream));
-                }
-                a.counts = c->counts + slot * kShards;
-            }
+            a.counts = cnt ? c->counts + (size_t)((c->turn + 1) % kRingSlots) * kShards : nullptr;
             HIP_OR_FAIL(c, golk::launch_step(a, c->fast, c->stream));
         }
         if (split) {   // join: the next launch overwrites rows the side launches read
@@ -2580,6 +2651,14 @@ int gol_tile_codes(int32_t *codes, int32_t cap)
     const int n = (int)std::size(golk::kTileCodes);
     if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
     for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileCodes[i];
+    return n;
+}
+
+int gol_tile_count_codes(int32_t *codes, int32_t cap)
+{
+    const int n = (int)std::size(golk::kTileCountCodes);
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileCountCodes[i];
     return n;
 }
 

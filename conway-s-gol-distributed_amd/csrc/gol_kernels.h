@@ -233,6 +233,32 @@ constexpr bool tile_code_shipped(int code)
         if (c == code) return true;
     return false;
 }
+// the codes k_step_tile_cnt is instantiated for (gol_tile.hip tile_cnt_kernel): K1t with the
+// per-turn alive counts fused, what a GOL_FLAG_COUNT_EVERY_TURN engine's multi-turn launches
+// run.  One word per lane; the pinned shapes' codes, both loop forms (turn pairs up to SEG 12,
+// one body above) and every turn order the searches pick, at the segments they pick most.  Each
+// one is pinned by tests/test_gpu_tile_counts.py through gol_tile_count_codes.
+constexpr int kTileCountCodes[] = {
+    4,   8,   16,                                                                // ORD 0
+    103, 104, 106, 108, 112, 116, 124,                                           // ORD 1
+    203, 204, 206, 208,                                                          // ORD 2
+    406, 416,                                                                    // ORD 4
+    503, 504, 506, 508, 512, 516, 524,                                           // ORD 5
+    616,                                                                         // ORD 6
+};
+constexpr bool tile_code_counted(int code)
+{
+    for (int c : kTileCountCodes)
+        if (c == code) return true;
+    return false;
+}
+constexpr bool tile_count_codes_shipped()
+{
+    for (int c : kTileCountCodes)
+        if (!tile_code_shipped(c) || c >= 1000) return false;
+    return true;
+}
+static_assert(tile_count_codes_shipped(), "kTileCountCodes: a subset of kTileCodes, W = 1");
 bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg);
 int tile_waves(int turns, int tile_h, int tile_w, int seg);
 // resident workgroups per CU of that launch (occupancy API: VGPRs, LDS; 0 on error)

@@ -117,6 +117,12 @@ constexpr int tile_slots_pow2(int threads)
     while (n < threads) n *= 2;
     return n;
 }
+// counted launches (k_step_tile_cnt), after the flags: one sum per (turn, wave), then one word
+// of row bits per thread
+constexpr size_t tile_count_lds_bytes(int threads)
+{
+    return 4 * (size_t)kMaxTileTurns * kTileMaxWaves + 4 * (size_t)threads;
+}
 constexpr size_t tile_lds_bytes_code(int threads, int code)
 {
     const int ord = code / 100 % 10;
@@ -148,7 +154,18 @@ struct RingArgs {
     int ablate;                 // (tools timing ablations, wrong boards: 1 no edge stores, 2 no
                                 // flag wait, 4 no ring loads)
 };
-template <int SEG, int ORD, int W, bool PERSIST, bool RING = false>
+// CNT (k_step_tile_cnt: GOL_FLAG_COUNT_EVERY_TURN on a K1t engine): after every turn t = 1 .. K
+// the alive cells of the tile's counted region go to a.counts[(t - 1) * kShards + shard], the
+// slot of turn turn0 + t (the engine passes K consecutive, zeroed slots).  The region is fixed
+// for the launch and is exactly what the final store writes, cut to rows [cnt_lo, cnt_hi):
+// tile rows [K, K + TH) below row_hi, interior lane columns inside the row -- every board word
+// belongs to one tile's region.  Per turn a counting wave popcounts its counted rows
+// (v_bcnt_u32_b32 accumulates: 2 VALU per row), reduces over its lanes by DPP and leaves the sum
+// in its own LDS word [t][wave]; nothing else is synchronised per turn (also under ORD 4's
+// flags).  Only the waves holding a row of [K, K + TH) count: they never leave the trapezoid,
+// and one of them adds the waves' sums up after one barrier at the end of the launch -- one
+// global atomic per (workgroup, turn) with a non-zero count.
+template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false>
 __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                                           uint64_t *__restrict__ out, const StepArgs &a,
                                           int turns, int tile, int ntx,
@@ -334,6 +351,84 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         if (lane == 0) flag[wave] = -1;
         __syncthreads();                                  // (once per launch)
     }
+    // CNT: the lane's counted rows are local rows [ci_lo, ci_hi) (none on a halo column, an
+    // idle lane or a column past the row's end); the waves w_lo .. w_hi hold the tile rows
+    // [K, K + TH), and their per-turn sums live after the flags: [turn][wave], 4 B each
+    static_assert(!CNT || (W == 1 && !PERSIST && !RING && ORD != 3 && ORD < 7),
+                  "counted launches: plain k_step_tile, one word per lane");
+    [[maybe_unused]] uint32_t *const csum = (uint32_t *)(xsh + 4 * (size_t)nslot * W) + kTileMaxWaves;
+    [[maybe_unused]] int cw_lo = 0, cw_hi = -1;
+    static_assert(!CNT || SEG <= 32, "counted launches: one word of row bits per lane");
+    [[maybe_unused]] bool cwave = false, cuni = false, cany = false;
+    // (the lane's row bits wait in LDS, after the sums: only a partly counted wave reads them)
+    [[maybe_unused]] uint32_t *const crow = csum + kMaxTileTurns * kTileMaxWaves;
+    if constexpr (CNT) {
+        cw_lo = K / (G * SEG);
+        cw_hi = min(nwaves - 1, (K + TH - 1) / (G * SEG));
+        cwave = wave >= cw_lo && wave <= cw_hi;          // (wave-uniform)
+        const int ybase = y0 - K + seg * SEG;            // buffer row of the lane's local row 0
+        const int ylo = max(y0, a.cnt_lo), yhi = min(min(y0 + TH, a.row_hi), a.cnt_hi);
+        const bool ccol = live && col >= 1 && col <= TW && x0 + col - 1 < nl;
+        const int ci_lo = min(max(ylo - ybase, 0), SEG), ci_hi = min(max(yhi - ybase, 0), SEG);
+        const int cn = ccol && cwave ? max(ci_hi - ci_lo, 0) : 0;
+        // bit i: the lane counts its local row i
+        crow[threadIdx.x] = cn > 0 ? (~0u >> (32 - cn)) << ci_lo : 0u;
+        cany = cn > 0;
+        // most waves hold only lanes that count every row or none: 2 VALU per row and one
+        // select; a wave with a partly counted segment masks row by row
+        cuni = __builtin_amdgcn_ballot_w64(cn != 0 && cn != SEG) == 0;
+    }
+    // (v_bcnt_u32_b32 adds to its second operand: one chain of 2 SEG instructions.  Written as
+    // popcount + sum the compiler counts every dword apart and adds the counts up as a tree, in
+    // 2 SEG more instructions and ~25 more registers)
+    auto bcnt = [](uint32_t x, uint32_t acc) {
+        uint32_t r;
+        asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+        return r;
+    };
+    auto bcnt0 = [](uint32_t x) {                        // (no register held for the zero)
+        uint32_t r;
+        asm("v_bcnt_u32_b32 %0, %1, 0" : "=v"(r) : "v"(x));
+        return r;
+    };
+    auto count_turn = [&](int t) {
+        if constexpr (CNT) {
+            if (!cwave) return;
+            uint32_t acc;
+            if (cuni) {
+                acc = bcnt(v[0][1], bcnt0(v[0][0]));
+#pragma unroll
+                for (int i = 1; i < SEG; ++i) acc = bcnt(v[i][1], bcnt(v[i][0], acc));
+                acc = cany ? acc : 0u;                  // (all of the lane's rows or none)
+            } else {
+                // (the lane index and the row bits are formed every turn behind an opaque
+                // mask: neither they nor the SEG row masks stay in registers across the turns)
+                uint32_t all = ~0u;
+                asm volatile("" : "+v"(all));
+                const uint32_t ln = __builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+                const uint32_t rlo = crow[wave * 64 + (int)ln];
+                acc = 0;
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) {
+                    const uint32_t m = 0u - ((rlo >> i) & 1u);
+                    acc = bcnt(v[i][1] & m, bcnt(v[i][0] & m, acc));
+                }
+                // (a DPP read needs 2 wait states after the VALU write of its source, and the
+                // compiler does not count an inline-asm instruction as that write)
+                asm("s_nop 1" : "+v"(acc));
+            }
+            // wave sum by DPP: inclusive scan within each row of 16 lanes (row_shr 1, 2, 4, 8),
+            // then row 15 of rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 / 3: lane 63 holds
+            // the total (at most 64 x SEG x 64 cells)
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x111, 0xf, 0xf, true);
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x112, 0xf, 0xf, true);
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x114, 0xf, 0xf, true);
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x118, 0xf, 0xf, true);
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x142, 0xa, 0xf, false);
+            acc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, 0x143, 0xc, 0xf, false);
+            if (lane == 63) csum[t * kTileMaxWaves + wave] = acc;
+        }
+    };
     auto publish = [&](int t) {
         if constexpr (ORD == 4) {
             asm volatile("" ::: "memory");
@@ -725,6 +820,7 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                 break;
             }
             turn(std::integral_constant<int, 0>{}, (t & 1) * 2 * nslot, t);
+            count_turn(t);
         }
     } else {
         for (int t = 0; t < K; t += 2) {
@@ -734,6 +830,7 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                 break;
             }
             turn(std::integral_constant<int, 0>{}, 0, t);
+            count_turn(t);
             if (t + 1 == K) break;
             if (!PERSIST && (wrow1 <= t + 1 || wrow0 > lastrow - t - 1)) {
                 leave(t + 1);
@@ -741,9 +838,25 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                 break;
             }
             turn(std::integral_constant<int, 1>{}, 0, t + 1);
+            count_turn(t + 1);
         }
     }
     if (!PERSIST && gone) return;
+    if constexpr (CNT) {
+        // the waves still here (a wave that left has ended: the barrier does not count it);
+        // wave cw_lo never leaves.  Its lane t adds turn t + 1's sums of the counting waves
+        __syncthreads();
+        uint32_t all = ~0u;
+        asm volatile("" : "+v"(all));
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+        if (wave == cw_lo && ln < K) {
+            uint32_t s = 0;
+            for (int w = cw_lo; w <= cw_hi; ++w) s += csum[ln * kTileMaxWaves + w];
+            if (s)
+                atomicAdd(a.counts + (size_t)ln * kShards + (blockIdx.x & (kShards - 1)),
+                          (unsigned long long)s);
+        }
+    }
     // interior rows [K, K + TH) of the tile, below row_hi; interior columns inside the row
     if (gone || !live || col < 1 || col > TW || x0 + col - 1 >= nl) return;
     const int t0 = seg * SEG + (rev ? SEG - 1 : 0);
@@ -986,6 +1099,18 @@ __global__ __launch_bounds__(1024, (ORD == 7 ? 6 : 1)) void k_step_tile(const ui
     const int tile = tile_of_block(ntiles);
     if (tile >= ntiles) return;                          // the whole workgroup
     tile_pass<SEG, ORD, W, false>(in, out, a, turns, tile, ntx);
+}
+
+// k_step_tile with the per-turn alive counts fused (tile_pass CNT; the instantiations:
+// golk::kTileCountCodes).  Its own entry point: the uncounted kernels stay as they are.
+template <int SEG, int ORD, int W>
+__global__ __launch_bounds__(1024, 1) void k_step_tile_cnt(const uint64_t *__restrict__ in,
+                                                           uint64_t *__restrict__ out, StepArgs a,
+                                                           int turns, int ntx, int ntiles)
+{
+    const int tile = tile_of_block(ntiles);
+    if (tile >= ntiles) return;                          // the whole workgroup
+    tile_pass<SEG, ORD, W, false, false, true>(in, out, a, turns, tile, ntx);
 }
 
 // ORD 3: tile pairs (tile_pass_pair).  Pair j runs tiles 2j and 2j + 1; with an odd count the

@@ -185,6 +185,39 @@ void *tile_kernel(int code)
     return ord == 2 ? tile_fn<2, 1>(seg) : ord ? tile_fn<1, 1>(seg) : tile_fn<0, 1>(seg);
 }
 
+// k_step_tile_cnt instantiations (the per-turn alive counts fused): kTileCountCodes
+void *tile_cnt_kernel(int code)
+{
+    static_assert(std::size(kTileCountCodes) == 24, "tile_cnt_kernel covers kTileCountCodes");
+    switch (code) {
+    case 4: return reinterpret_cast<void *>(&k_step_tile_cnt<4, 0, 1>);
+    case 8: return reinterpret_cast<void *>(&k_step_tile_cnt<8, 0, 1>);
+    case 16: return reinterpret_cast<void *>(&k_step_tile_cnt<16, 0, 1>);
+    case 103: return reinterpret_cast<void *>(&k_step_tile_cnt<3, 1, 1>);
+    case 104: return reinterpret_cast<void *>(&k_step_tile_cnt<4, 1, 1>);
+    case 106: return reinterpret_cast<void *>(&k_step_tile_cnt<6, 1, 1>);
+    case 108: return reinterpret_cast<void *>(&k_step_tile_cnt<8, 1, 1>);
+    case 112: return reinterpret_cast<void *>(&k_step_tile_cnt<12, 1, 1>);
+    case 116: return reinterpret_cast<void *>(&k_step_tile_cnt<16, 1, 1>);
+    case 124: return reinterpret_cast<void *>(&k_step_tile_cnt<24, 1, 1>);
+    case 203: return reinterpret_cast<void *>(&k_step_tile_cnt<3, 2, 1>);
+    case 204: return reinterpret_cast<void *>(&k_step_tile_cnt<4, 2, 1>);
+    case 206: return reinterpret_cast<void *>(&k_step_tile_cnt<6, 2, 1>);
+    case 208: return reinterpret_cast<void *>(&k_step_tile_cnt<8, 2, 1>);
+    case 406: return reinterpret_cast<void *>(&k_step_tile_cnt<6, 4, 1>);
+    case 416: return reinterpret_cast<void *>(&k_step_tile_cnt<16, 4, 1>);
+    case 503: return reinterpret_cast<void *>(&k_step_tile_cnt<3, 5, 1>);
+    case 504: return reinterpret_cast<void *>(&k_step_tile_cnt<4, 5, 1>);
+    case 506: return reinterpret_cast<void *>(&k_step_tile_cnt<6, 5, 1>);
+    case 508: return reinterpret_cast<void *>(&k_step_tile_cnt<8, 5, 1>);
+    case 512: return reinterpret_cast<void *>(&k_step_tile_cnt<12, 5, 1>);
+    case 516: return reinterpret_cast<void *>(&k_step_tile_cnt<16, 5, 1>);
+    case 524: return reinterpret_cast<void *>(&k_step_tile_cnt<24, 5, 1>);
+    case 616: return reinterpret_cast<void *>(&k_step_tile_cnt<16, 6, 1>);
+    default: return nullptr;
+    }
+}
+
 bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg)
 {
     if (turns < 2 || turns > 64 || tile_h < 1 || tile_w < 1 || tile_w + 2 > 64 || !tile_kernel(seg))
@@ -249,14 +282,19 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
     const long long units = GOL_TILE_PAIR && a.tile_seg / 100 == 3 ? (ntiles + 1) / 2 : ntiles;
     const unsigned blocks = (unsigned)((units + 7) / 8 * 8);
     const int threads = 64 * tile_waves(turns, a.band, a.tile_w, a.tile_seg);
-    void *fn = tile_kernel(a.tile_seg);
+    // a.counts: `turns` consecutive zeroed slots of kShards accumulators, one per turn of the
+    // launch -- the counted kernel, and an error for a code without one (never the uncounted
+    // kernel with the counts dropped)
+    void *fn = a.counts ? tile_cnt_kernel(a.tile_seg) : tile_kernel(a.tile_seg);
+    if (!fn || (a.counts && !tile_code_counted(a.tile_seg))) return hipErrorInvalidValue;
     StepArgs args = a;
     const uint64_t *in = a.in;
     uint64_t *out = a.out;
     int k = turns, ntx_arg = ntx, nt = (int)ntiles;
     void *params[] = {&in, &out, &args, &k, &ntx_arg, &nt};
     return hipLaunchKernel(fn, dim3(blocks), dim3(threads), params,
-                           tile_lds_bytes_code(threads, a.tile_seg), s);
+                           tile_lds_bytes_code(threads, a.tile_seg) + (a.counts ? tile_count_lds_bytes(threads) : 0),
+                           s);
 }
 
 }  // namespace golk

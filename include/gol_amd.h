@@ -70,7 +70,12 @@ extern "C" {
 typedef struct gol_ctx gol_ctx;
 
 /* flags */
-#define GOL_FLAG_COUNT_EVERY_TURN  0x1u  /* fuse a popcount into every turn (per-turn series) */
+#define GOL_FLAG_COUNT_EVERY_TURN  0x1u  /* record the alive count of every turn (gol_turn_counts).
+                                            The count is fused into the one-turn stencil and into
+                                            k_step_tile: an engine whose multi-turn kernel is
+                                            k_step_tile at a gol_tile_count_codes code keeps its
+                                            temporal blocking, every other one runs one turn per
+                                            launch */
 #define GOL_FLAG_FORCE_GENERIC     0x2u  /* use the generic stencil even when the fast one applies */
 #define GOL_FLAG_NO_AUTOTUNE       0x4u  /* skip the create-time (turns per launch, band) timing
                                             sweep on large boards (results never depend on it) */
@@ -184,6 +189,9 @@ int gol_last_launch_tiles(gol_ctx *ctx, int32_t *tile_w, int32_t *tile_seg, int3
  * tests: every code the shape search can pick has an oracle test).  Writes min(n, cap) codes,
  * returns n.  Needs no device. */
 int gol_tile_codes(int32_t *codes, int32_t cap);
+/* The subset with a counted form (k_step_tile with the per-turn alive counts fused): the codes
+ * a GOL_FLAG_COUNT_EVERY_TURN engine runs multi-turn launches on; same convention. */
+int gol_tile_count_codes(int32_t *codes, int32_t cap);
 /* The subset of those the persistent tile kernel (K1p: small torus boards, tiles resident
  * across blocks of turns) runs; same convention. */
 int gol_tile_persist_codes(int32_t *codes, int32_t cap);
