@@ -1,5 +1,5 @@
 // Internal launch interface of the gfx950 kernels (gol_kernels.hip).
-// Not part of the C ABI; the engine (gol_engine.cpp) is the only caller.
+// Not part of the C ABI; the engine's units (gol_ctx.h lists them) are the only callers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,698 @@
+// gol_step.cpp — the launch planner, gol_step / gol_step_overlap and the read-job queue.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <iterator>
+
+#include "gol_ctx.h"
+
+using namespace goleng;
+
+namespace goleng {
+
+void set_shape(gol_ctx *c, LaunchShape s)
+{
+    c->shape = std::move(s);
+    for (int &b : c->band_at) b = 0;
+}
+
+golk::StepArgs whole_buffer_args(const gol_ctx *c)
+{
+    golk::StepArgs a{};
+    a.width = c->cfg.width;
+    a.nw = c->nw;
+    a.pitch = c->pitch;
+    a.modrows = c->buf_rows;
+    a.row_lo = 0;
+    a.row_hi = c->buf_rows;
+    a.cnt_lo = own_lo(c);
+    a.cnt_hi = own_hi(c);
+    a.variant = c->variant;
+    a.multi_words = c->multi_words;
+    a.wg_prio = c->wg_prio;
+    a.err = c->d_err;
+    return a;
+}
+
+// The temporal-blocking kernel runs on the interleaved word layout (gol_kernels.h,
+// multi_is_il); everything else -- the k = 1 stencils, PGM pack/unpack, the alive list,
+// reads, loads, halo rows crossing the API -- sees the standard layout.  The engine
+// converts lazily, whole buffer, when the next consumer needs the other layout (one read
+// and one write of the board: at most twice per gol_step, never inside a run of
+// multi-turn launches).  Popcounts do not depend on the layout.
+int ensure_layout(gol_ctx *c, bool il)
+{
+    if (c->il == il) return GOL_OK;
+    HIP_OR_FAIL(c, golk::launch_il_convert(c->board[c->cur], c->pitch, c->board[c->cur ^ 1],
+                                           c->pitch, c->buf_rows, c->nw, il, c->stream));
+    c->cur ^= 1;
+    c->il = il;
+    c->prev_valid = false;                   // the conversion overwrote the previous board
+    return GOL_OK;
+}
+
+// The band a kernel tuned at (K0, band0) runs at depth k.  A launch of another depth -- the
+// even split's shallower launches, a short gol_step, the last block before a halo exchange,
+// a planned launch -- runs a kernel with another residency (k_step_wg: 4..8 waves per
+// workgroup at 7 or 8 waves per SIMD; k_step_skew: 2..4 waves per SIMD), where band0 would
+// leave resident slots idle or spill a few pipelines into one more round (65536^2: K = 16's
+// band 607 fills 1791 of 1792 slots; a K = 20 launch has 1280).  Keep the tuned number of
+// rounds instead: the smallest band whose grid fits them at depth k (kMultiWgPg: the next
+// band it runs at).
+int band_same_rounds(const gol_ctx *c, int var, int K0, int band0, int k)
+{
+    if (k == K0 || k < 2 || k > golk::kMaxTurnsPerLaunch || var == golk::kMultiTile)
+        return band0;                        // (k_step_tile: the tile height stays)
+    const int lane_dw = golk::multi_lane_dwords(c->multi_words, var);
+    const int per = golk::multi_pipes_per_block(var);
+    const long long cap_t = (long long)c->ncu * golk::multi_blocks_per_cu(K0, c->multi_words, var) * per;
+    const long long cap_k = (long long)c->ncu * golk::multi_blocks_per_cu(k, c->multi_words, var) * per;
+    if (cap_t <= 0 || cap_k <= 0) return band0;
+    const int W = c->cfg.width, rows = c->buf_rows;
+    const long long pipes = golk::multi_pipes(W, rows, band0, lane_dw, var);
+    const long long rounds = std::max(1ll, (pipes + cap_t - 1) / cap_t);
+    int b = band0;
+    for (int band = 16; band <= std::max(rows, 16); ++band)
+        if (golk::multi_pipes(W, rows, band, lane_dw, var) <= rounds * cap_k) {
+            b = band;
+            break;
+        }
+    const bool ser = var == golk::kMultiWgPgS;
+    if (golk::is_pg_variant(var) && golk::pg_ok(k, golk::pg_band(k, b, ser), ser))
+        b = golk::pg_band(k, b, ser);
+    return b;
+}
+
+// the word layout a launch of depth k runs on
+bool stepping_il(const gol_ctx *c, int k)
+{
+    return k > 1 && golk::multi_is_il(c->multi_words, c->shape.multi_variant);
+}
+
+}  // namespace goleng
+
+namespace {
+
+// band_same_rounds for the engine's kernel and depth (cached per shape: set_shape resets the
+// cache, this fills it); a band the caller fixed (gol_config.band_rows) is kept
+int band_for_depth(gol_ctx *c, int k)
+{
+    const LaunchShape &s = c->shape;
+    if (s.short_k > 0 && s.multi_variant == golk::kMultiTile && c->cfg.band_rows <= 0 &&
+        k >= 2 && k <= s.short_k)
+        return s.short_band;
+    if (k == s.tpl || c->cfg.band_rows > 0 || k < 2 || k > golk::kMaxTurnsPerLaunch)
+        return s.band_multi;
+    int &b = c->band_at[k];
+    if (b <= 0) b = band_same_rounds(c, s.multi_variant, s.tpl, s.band_multi, k);
+    return b;
+}
+
+// A count engine (GOL_FLAG_COUNT_EVERY_TURN) runs multi-turn launches only on k_step_tile at
+// a code with a counted instantiation (golk::kTileCountCodes); every other count engine -- K1s
+// / K1w kernels, a GOL_TILE code without one, generic widths, blocking_limited,
+// GOL_COUNT_BLOCKING=0 -- runs one-turn launches with the count fused into the stencil.
+bool count_fused(const gol_ctx *c)
+{
+    return (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) && c->count_blocking && c->shape.tpl > 1 &&
+           c->shape.multi_variant == golk::kMultiTile && golk::tile_code_counted(c->shape.tile_seg);
+}
+
+}  // namespace
+
+namespace goleng {
+
+// The next launch when `room` turns remain before the next sync point (end of the gol_step
+// call, or the next halo exchange of a strip engine).  k = 1: the one-turn kernel.
+//  * Autotuned engines follow the launch plan for room <= kPlanMax: the sequence of launches
+//    (depth and kernel) the create-time timing table says is fastest.  A short launch costs
+//    nearly as much as a full one and the kernels differ in that fixed cost (65536^2,
+//    profiles/r02_launch_table_65536.log: k_step_skew 260 us at K = 6 and 384 at K = 10;
+//    k_step_wg 413 us at K = 4, 459 at 12, 595 at 16), so 20 turns run best as 10 + 10 on
+//    k_step_skew although k_step_wg at K = 16 is the fastest per turn.  Longer stretches run
+//    full launches of the tuned kernel and depth first.
+//  * Otherwise the turns are spread over ceil(room / tpl) launches of near-equal depth: 128
+//    turns at tpl 6 run as 18 x 6 + 4 x 5, not 21 x 6 + 2.
+// gol_step and gol_halo_buffers both use this rule (the zero-copy halo layout must be the
+// layout the first launch after an exchange runs on; every planned kernel runs on the
+// interleaved layout).
+Launch plan_launch(gol_ctx *c, int64_t room)
+{
+    const LaunchShape &s = c->shape;
+    Launch L{1, s.multi_variant, c->band, 0, 0};
+    if (s.tpl <= 1 || room < 2 || c->blocked_pending) return L;
+    if (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) {
+        if (!count_fused(c)) return L;
+        // a counted launch adds into K consecutive slots of the count ring: it ends at the
+        // ring's last slot at the latest (once per kRingSlots turns).  No K1p / K1q, no timed
+        // plans (they mix kernels without a counted form): the even split at the tuned depth.
+        room = std::min<int64_t>(room, kRingSlots - (c->turn + 1) % kRingSlots);
+        if (room < 2) return L;
+        const int64_t nl = (room + s.tpl - 1) / s.tpl;
+        const int k = (int)((room + nl - 1) / nl);
+        const int band = band_for_depth(c, k);
+        if (!golk::multi_ok(c->cfg.width, k, s.multi_variant) ||
+            !golk::tile_shape_ok(c->nw, k, band, s.tile_w, s.tile_seg))
+            return L;
+        return Launch{k, s.multi_variant, band, s.tile_w, s.tile_seg};
+    }
+    if (blocks_plan(c, room, &L)) return L;  // K1p / K1q (tools build)
+    if (!s.plan.empty()) {
+        if (room > kPlanMax)
+            return Launch{s.tpl, s.multi_variant, s.band_multi, s.tile_w, s.tile_seg};
+        if (s.plan[room].k >= 2) return s.plan[room];
+    }
+    const int64_t nl = (room + s.tpl - 1) / s.tpl;
+    const int k = (int)((room + nl - 1) / nl);
+    if (!golk::multi_ok(c->cfg.width, k, s.multi_variant)) return L;
+    return Launch{k, s.multi_variant, band_for_depth(c, k), s.tile_w, s.tile_seg};
+}
+
+// kMultiWgPg: the published-row scratch and flags for a launch of `a`, grown on demand (the
+// engine's streams are drained first: a running launch may still use the old buffers), and
+// a fresh epoch.  Other variants, and bands the kernel runs as kMultiWgHx, need nothing.
+hipError_t pg_prepare(gol_ctx *c, golk::StepArgs &a, int k)
+{
+    a.xrows = nullptr;
+    a.xflags = nullptr;
+    if (!golk::is_pg_variant(a.multi_variant) ||
+        !golk::pg_ok(k, a.band, a.multi_variant == golk::kMultiWgPgS))
+        return hipSuccess;
+    if (!device_exclusive(c->device)) {      // (launch_wg runs it as plain helix bands)
+        a.multi_variant = a.multi_variant == golk::kMultiWgPgS ? golk::kMultiWgHxS
+                                                               : golk::kMultiWgHx;
+        return hipSuccess;
+    }
+    const long long T =
+        golk::multi_pipes(a.width, a.row_hi - a.row_lo, a.band, 2, a.multi_variant);
+    const size_t lanes = (size_t)T * 62 + 64;
+    if (lanes > c->pg_lanes || (size_t)T > c->pg_tiles) {
+        if (2ull * golk::kPgStages * lanes * 8 >= (1ull << 31)) return hipSuccess;   // helix
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess && c->side) e = hipStreamSynchronize(c->side);
+        if (e != hipSuccess) return e;
+        if (c->pg_rows) (void)hipFree(c->pg_rows);
+        if (c->pg_flags) (void)hipFree(c->pg_flags);
+        c->pg_rows = nullptr;
+        c->pg_flags = nullptr;
+        c->pg_lanes = c->pg_tiles = 0;
+        e = hipExtMallocWithFlags((void **)&c->pg_rows, 2ull * golk::kPgStages * lanes * 8,
+                                  hipDeviceMallocUncached);
+        if (e == hipSuccess)
+            e = hipExtMallocWithFlags((void **)&c->pg_flags,
+                                      (size_t)T * golk::kPgStages * sizeof(unsigned),
+                                      hipDeviceMallocUncached);
+        if (e == hipSuccess)
+            e = hipMemset(c->pg_flags, 0, (size_t)T * golk::kPgStages * sizeof(unsigned));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) return e;
+        c->pg_lanes = lanes;
+        c->pg_tiles = (size_t)T;
+    }
+    a.xrows = c->pg_rows;
+    a.xflags = c->pg_flags;
+    a.xlanes = (unsigned)c->pg_lanes;
+    a.epoch = ++c->pg_epoch;
+    return hipSuccess;
+}
+
+}  // namespace goleng
+
+namespace {
+
+// Serve the read-only calls posted by run_read (the stepping thread, holding `mu`).
+void serve_jobs(gol_ctx *c)
+{
+    std::vector<Job *> js;
+    {
+        std::lock_guard<std::mutex> jl(c->jm);
+        js.swap(c->jobs);
+        c->jobs_pending.store(false);
+    }
+    for (Job *j : js) {
+        const int rc = j->fn();
+        std::lock_guard<std::mutex> jl(c->jm);
+        j->rc = rc;
+        j->done = true;                      // (j lives on the waiter's stack: not touched again)
+    }
+    if (!js.empty()) c->jcv.notify_all();
+}
+
+void set_stepping(gol_ctx *c, bool on)
+{
+    std::lock_guard<std::mutex> jl(c->jm);
+    c->stepping = on;
+}
+
+#if GOL_TOOLS
+// Tools build only (GOL_MULTI_VARIANT=kMultiWgDiag): one k_step_wg launch with per-wave wait
+// timing, summarised by wave role on stderr.  (C linkage: the library exports this name.)
+extern "C" int wg_diag_launch(gol_ctx *c, golk::StepArgs a, int k)
+{
+    const long long ntx = golk::multi_tiles(c->cfg.width, 2);
+    const long long pipes = ntx * ((a.row_hi - a.row_lo + a.band - 1) / a.band);
+    const size_t n = (size_t)pipes * 4 * 10;
+    unsigned long long *d = nullptr;
+    HIP_OR_FAIL(c, hipMalloc(&d, n * 8));
+    HIP_OR_FAIL(c, hipMemsetAsync(d, 0, n * 8, c->stream));
+    a.counts = d;
+    HIP_OR_FAIL(c, golk::launch_step_multi(a, k, c->stream));
+    std::vector<unsigned long long> h(n);
+    HIP_OR_FAIL(c, hipMemcpyAsync(h.data(), d, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(d);
+    unsigned long long t0min = ~0ull, t1max = 0;
+    std::vector<unsigned long long> starts, ends;        // wave 0's start / wave 3's end
+    for (long long p = 0; p < pipes; ++p)
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long *e = &h[((size_t)p * 4 + w) * 10];
+            if (e[8] == 0) continue;                     // a workgroup past the last band
+            t0min = std::min(t0min, e[8]);
+            t1max = std::max(t1max, e[9]);
+            if (w == 0) starts.push_back(e[8]);
+            if (w == 3) ends.push_back(e[9]);
+        }
+    auto pct = [](std::vector<unsigned long long> v, unsigned long long base, double q) {
+        if (v.empty()) return 0.0;
+        std::sort(v.begin(), v.end());
+        return (double)(v[(size_t)(q * (double)(v.size() - 1))] - base);
+    };
+    fprintf(stderr,
+            "wg_diag starts (100 MHz ticks after the first) p10 %.0f p50 %.0f p90 %.0f max %.0f; "
+            "ends p10 %.0f p50 %.0f p90 %.0f max %.0f\n",
+            pct(starts, t0min, 0.1), pct(starts, t0min, 0.5), pct(starts, t0min, 0.9),
+            pct(starts, t0min, 1.0), pct(ends, t0min, 0.1), pct(ends, t0min, 0.5),
+            pct(ends, t0min, 0.9), pct(ends, t0min, 1.0));
+    for (int w = 0; w < 4; ++w) {
+        double life = 0, first = 0, fw = 0, nf = 0, ew = 0, ne = 0, nl = 0;
+        for (long long p = 0; p < pipes; ++p) {
+            const unsigned long long *e = &h[((size_t)p * 4 + w) * 10];
+            life += (double)e[0]; first += (double)e[1]; fw += (double)e[2];
+            nf += (double)e[3]; ew += (double)e[4]; ne += (double)e[5]; nl += (double)e[6];
+        }
+        fprintf(stderr,
+                "wg_diag K=%d band=%d pipes=%lld wave %d: life %.0f ticks, first-row wait %.1f%%, "
+                "fetch waits %.1f%% (%.2f per row), emit waits %.1f%% (%.2f per row)\n",
+                k, a.band, pipes, w, life / pipes, 100 * first / life, 100 * fw / life, nf / nl,
+                100 * ew / life, ne / nl);
+    }
+    fprintf(stderr, "wg_diag launch span %llu ticks of 100 MHz\n", t1max - t0min);
+    return GOL_OK;
+}
+#endif  // GOL_TOOLS
+
+constexpr int kCtlDepth = 2;   // launches queued ahead while a control word is in use
+
+// read-only calls from other threads are served at launch boundaries while one of these lives
+struct Stepping {
+    gol_ctx *c;
+    explicit Stepping(gol_ctx *c_) : c(c_) { set_stepping(c, true); }
+    ~Stepping()
+    {
+        set_stepping(c, false);              // later readers take the lock themselves
+        serve_jobs(c);
+    }
+};
+
+// control word: with a controlling thread present, keep at most kCtlDepth launches
+// queued so a pause / stop takes effect within that many launches (and so does a reader:
+// once one has been served during a step, steps keep the queue this short)
+struct EventRing {
+    hipEvent_t ev[kCtlDepth] = {};
+    int n = 0;
+    ~EventRing()
+    {
+        for (int i = 0; i < std::min(n, kCtlDepth); ++i) (void)hipEventDestroy(ev[i]);
+    }
+};
+
+// bound the queue: wait for the launch kCtlDepth back, then mark this one
+int bound_queue(gol_ctx *c, EventRing &ring)
+{
+    hipEvent_t &e = ring.ev[ring.n % kCtlDepth];
+    if (ring.n >= kCtlDepth) {
+        HIP_OR_FAIL(c, hipEventSynchronize(e));
+        if (int rc = check_dev_err(c)) return rc;
+    } else {
+        HIP_OR_FAIL(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    HIP_OR_FAIL(c, hipEventRecord(e, c->stream));
+    ++ring.n;
+    return GOL_OK;
+}
+
+// The control word at a launch boundary: GOL_OK to go on, GOL_STOPPED, or an error.
+int obey_control(gol_ctx *c, std::unique_lock<std::recursive_mutex> &lk, long long *zero_hi)
+{
+    int w = c->control.load();
+    if (w == GOL_CONTROL_PAUSE) {
+        // park at this launch boundary with the board complete (Server/gol/
+        // distributor.go:147-156: the turn loop blocks until the second 'p'); the
+        // engine is released while parked, so AliveCellsCount / GetWorld calls from
+        // other threads run at once (the reference's ticker keeps firing while paused,
+        // Local/gol/distributor.go:117-130,154-167)
+        if (int rc = sync_checked(c)) return rc;
+        set_stepping(c, false);
+        serve_jobs(c);
+        c->parked.store(true);
+        lk.unlock();
+        while ((w = c->control.load()) == GOL_CONTROL_PAUSE)
+            std::this_thread::sleep_for(std::chrono::microseconds(200));
+        lk.lock();
+        *zero_hi = c->turn;                  // (the engine was released: zero again from here)
+        set_stepping(c, true);
+        c->parked.store(false);
+    }
+    // quit / kill (distributor.go:143-146,157-164)
+    return w == GOL_CONTROL_STOP ? GOL_STOPPED : GOL_OK;
+}
+
+// Count engines: zero the count slots of a launch's turns c->turn + 1 .. c->turn + k (zero_hi:
+// the last turn whose slot this step has zeroed; `left`: the turns the step still has to run).
+// One memset clears from the first slot not yet zeroed to the end of its batch of kRingAhead
+// slots (a batch never wraps the ring), but no further than the step's last turn and never
+// past turn c->turn + kRingAhead: the slots up to there hold turns <= c->turn - kRing, which
+// gol_turn_counts no longer accepts, now or at any later launch boundary.  A launch that
+// straddles a batch boundary takes a second memset (k <= kRingAhead).
+int zero_count_slots(gol_ctx *c, int k, int64_t left, long long *zero_hi)
+{
+    *zero_hi = std::max(*zero_hi, c->turn);
+    while (*zero_hi < c->turn + k) {
+        const long long z = *zero_hi + 1;
+        const size_t slot = (size_t)(z % kRingSlots);
+        const long long e = std::min({z + (long long)(kRingAhead - slot % kRingAhead) - 1,
+                                      c->turn + (long long)kRingAhead,
+                                      c->turn + (long long)left});
+        HIP_OR_FAIL(c, hipMemsetAsync(c->counts + slot * kShards, 0,
+                                      (size_t)(e - z + 1) * kShards * 8, c->stream));
+        *zero_hi = e;
+    }
+    return GOL_OK;
+}
+
+// the count slot of the engine's next turn
+unsigned long long *next_count_slot(gol_ctx *c)
+{
+    return c->counts + (size_t)((c->turn + 1) % kRingSlots) * kShards;
+}
+
+// One launch of k > 1 turns as planned.  split: the interior output rows [in_lo, in_hi) on the
+// engine stream at once, the rows next to the halos on the side stream.
+int launch_multi(gol_ctx *c, golk::StepArgs a, const Launch &plan, bool cnt, bool split,
+                 int in_lo, int in_hi)
+{
+    const int k = plan.k;
+    a.blocked = nullptr;
+    // (a count engine's multi-turn launch: k_step_tile_cnt, k consecutive slots --
+    // plan_launch stops at the ring's end)
+    a.counts = cnt ? next_count_slot(c) : nullptr;
+    a.band = plan.band;
+    a.multi_variant = plan.var;
+    const bool blocks = plan.var == golk::kMultiTilePersist || plan.var == golk::kMultiTileStream;
+    if (plan.var == golk::kMultiTile || blocks) {
+        a.tile_w = plan.tw;
+        a.tile_seg = plan.seg;
+    }
+#if GOL_TOOLS
+    if (c->shape.multi_variant == golk::kMultiWgDiag && !split) return wg_diag_launch(c, a, k);
+#endif
+    if (blocks) {
+        HIP_OR_FAIL(c, blocks_launch(c, a, plan));
+    } else if (split && in_lo < in_hi) {
+        golk::StepArgs b = a;
+        // concurrent launches cannot share the published-row scratch
+        if (b.multi_variant == golk::kMultiWgPg) b.multi_variant = golk::kMultiWgHx;
+        if (b.multi_variant == golk::kMultiWgPgS) b.multi_variant = golk::kMultiWgHxS;
+        b.row_lo = in_lo;
+        b.row_hi = in_hi;
+        HIP_OR_FAIL(c, golk::launch_step_multi(b, k, c->stream));
+        // boundary rows: short bands so the few rows still spread over many waves
+        b.band = std::min(c->shape.band_multi, golk::kOverlapBand);
+        b.row_lo = a.row_lo;
+        b.row_hi = in_lo;
+        HIP_OR_FAIL(c, golk::launch_step_multi(b, k, c->side));
+        b.row_lo = in_hi;
+        b.row_hi = a.row_hi;
+        HIP_OR_FAIL(c, golk::launch_step_multi(b, k, c->side));
+    } else {
+        HIP_OR_FAIL(c, pg_prepare(c, a, k));
+        HIP_OR_FAIL(c, golk::launch_step_multi(a, k, split ? c->side : c->stream));
+    }
+    return GOL_OK;
+}
+
+// One one-turn launch.  split: interior now, the 2 x (halo) boundary rows after the receives.
+int launch_one(gol_ctx *c, golk::StepArgs a, bool cnt, bool split, int in_lo, int in_hi)
+{
+    a.blocked = c->blocked_pending ? c->blocked : nullptr;
+    if (!split) {
+        a.counts = cnt ? next_count_slot(c) : nullptr;
+        HIP_OR_FAIL(c, golk::launch_step(a, c->fast, c->stream));
+        return GOL_OK;
+    }
+    a.counts = nullptr;
+    golk::StepArgs b = a;
+    if (in_lo < in_hi) {
+        b.row_lo = in_lo;
+        b.row_hi = in_hi;
+        HIP_OR_FAIL(c, golk::launch_step(b, c->fast, c->stream));
+        b.row_lo = a.row_lo;
+        b.row_hi = in_lo;
+        HIP_OR_FAIL(c, golk::launch_step(b, c->fast, c->side));
+        b.row_lo = in_hi;
+        b.row_hi = a.row_hi;
+        HIP_OR_FAIL(c, golk::launch_step(b, c->fast, c->side));
+    } else {
+        HIP_OR_FAIL(c, golk::launch_step(a, c->fast, c->side));
+    }
+    return GOL_OK;
+}
+
+// gol_step / gol_step_overlap.  xstream != null: the first launch is split -- the rows
+// whose k-turn dependency cone stays inside the owned rows run on the engine stream at
+// once, the rows next to the halos run on the side stream after everything queued on
+// xstream (the caller's halo receives) -- and the engine stream joins the side stream
+// before the next launch.  (C linkage: the library exports this name.)
+extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
+              std::unique_lock<std::recursive_mutex> &lk)
+{
+    if (is_strip(c) && turns > c->halo_valid)
+        return fail(c, GOL_ESTATE, "strip engine: %lld turns requested, halos valid for %d",
+                    (long long)turns, c->halo_valid);
+    DeviceGuard g(c->device);
+    const bool cnt = (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) != 0;
+    golk::StepArgs a = whole_buffer_args(c);
+    a.band = c->band;
+    a.multi_variant = c->shape.multi_variant;
+    a.tile_w = c->shape.tile_w;
+    a.tile_seg = c->shape.tile_seg;
+    Stepping stepping(c);
+    EventRing ring;
+    const bool ctl = c->control_used.load();
+    // a reader served during an earlier step does not shorten this one's queue: the bound
+    // comes back when a reader is served during this step (a ticker's snapshot)
+    c->readers.store(false);
+    // a short torus step runs the sequence the autotune timed for exactly this many turns
+    const auto &seq = c->shape.seq;
+    const std::vector<Launch> *fixed =
+        !is_strip(c) && !cnt && !c->blocked_pending && turns >= 2 && turns <= kSeqMax &&
+                turns < (int64_t)seq.size() && !seq[turns].empty()
+            ? &seq[turns]
+            : nullptr;
+    size_t fi = 0;
+    long long zero_hi = c->turn;             // count engines: see zero_count_slots
+    c->last.clear();
+    c->last_n = 0;
+    for (int64_t t = 0; t < turns;) {
+        if (c->jobs_pending.load(std::memory_order_relaxed)) serve_jobs(c);
+        if (ctl)
+            if (int rc = obey_control(c, lk, &zero_hi)) return rc;
+        int64_t room = turns - t;
+        if (is_strip(c)) room = std::min<int64_t>(room, c->halo_valid);
+        const Launch plan = fixed && fi < fixed->size() ? (*fixed)[fi++] : plan_launch(c, room);
+        const int k = plan.k;
+        // rows computed: torus -> all; strip -> [s, buf_rows - s) after turn s since exchange
+        const int s0 = is_strip(c) ? c->cfg.halo - c->halo_valid : 0;
+        if (is_strip(c)) {
+            a.row_lo = s0 + k;
+            a.row_hi = c->buf_rows - s0 - k;
+        } else {
+            a.row_lo = 0;
+            a.row_hi = c->buf_rows;
+        }
+        // an overlapped window whose first launch runs on the other word layout (a one-turn
+        // window on an engine of multi-turn launches): the conversion reads the halo rows, so
+        // it follows the caller's receives -- gol_halo_buffers handed out rows of this board
+        if (xstream && t == 0 && c->il != stepping_il(c, k)) {
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_side, xstream));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        }
+        if (int rc = ensure_layout(c, stepping_il(c, k))) return rc;
+        a.in = c->board[c->cur];
+        a.out = c->board[c->cur ^ 1];
+        // split this launch around the incoming halos (first launch of an overlapped step;
+        // with per-turn counts the launch waits for the receives whole instead)
+        const bool split = xstream && t == 0 && is_strip(c) && !cnt;
+        if (xstream && t == 0 && !split) {
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_side, xstream));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        }
+        const int H = c->cfg.halo;
+        const int in_lo = H + k, in_hi = H + c->cfg.rows - k;   // interior output rows
+        if (split) {
+            // side stream: after the caller's receives (and the engine's queued work)
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_main, c->stream));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_side, xstream));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->side, c->ev_side, 0));
+        }
+        if (cnt)
+            if (int rc = zero_count_slots(c, k, turns - t, &zero_hi)) return rc;
+        if (int rc = k > 1 ? launch_multi(c, a, plan, cnt, split, in_lo, in_hi)
+                           : launch_one(c, a, cnt, split, in_lo, in_hi))
+            return rc;
+        if (split) {   // join: the next launch overwrites rows the side launches read
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_side, c->side));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->ev_side, 0));
+        }
+        c->cur ^= 1;
+        // a step of exactly one turn leaves the board one turn back in the other half, both in
+        // the standard layout; a longer step never does for its caller, however it was cut
+        // into launches (a board without multi-turn kernels runs it as one-turn launches)
+        c->prev_valid = k == 1 && turns == 1;
+        c->turn += k;
+        c->progress.store(c->turn);
+        c->launches += 1;
+        if (c->last.size() < kLastCap)
+            c->last.push_back(k > 1 ? plan : Launch{1, 0, c->band, 0, 0});
+        ++c->last_n;
+        t += k;
+        if (is_strip(c)) c->halo_valid -= k;
+        if (c->blocked_pending) {
+            // every cell is 0/255 after the first turn; the mask is dead from here on
+            c->blocked_pending = false;
+            c->raw_turn0.clear();
+        }
+        if (ctl || c->readers.load(std::memory_order_relaxed))
+            if (int rc = bound_queue(c, ring)) return rc;
+    }
+    if (c->blocked && !c->blocked_pending) {
+        HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+        release_blocked(c);
+    }
+    return GOL_OK;
+}
+
+}  // namespace
+
+// ================================================================ C ABI
+extern "C" {
+
+int gol_step(gol_ctx *c, int64_t turns)
+{
+    if (!c || turns < 0) return GOL_EINVAL;
+    std::unique_lock<std::recursive_mutex> lk(c->mu);
+    return step_impl(c, turns, nullptr, lk);
+}
+
+int gol_last_launches(gol_ctx *c, int32_t *turns, int32_t *kernel, int32_t *band, int32_t cap)
+{
+    if (!c || cap < 0 || (cap > 0 && (!turns || !kernel || !band))) return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const int n = (int)std::min<size_t>((size_t)cap, c->last.size());
+    for (int i = 0; i < n; ++i) {
+        turns[i] = c->last[i].k;
+        kernel[i] = c->last[i].var;
+        band[i] = c->last[i].band;
+    }
+    return (int)std::min<long long>(c->last_n, 0x7fffffff);
+}
+
+int gol_last_launch_tiles(gol_ctx *c, int32_t *tile_w, int32_t *tile_seg, int32_t *waves,
+                          int32_t *block_turns, int32_t cap)
+{
+    if (!c || cap < 0 || (cap > 0 && (!tile_w || !tile_seg || !waves || !block_turns)))
+        return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const int n = (int)std::min<size_t>((size_t)cap, c->last.size());
+    for (int i = 0; i < n; ++i) {
+        const Launch &L = c->last[i];
+        const bool p = L.var == golk::kMultiTilePersist || L.var == golk::kMultiTileStream;
+        const bool t = L.k > 1 && (L.var == golk::kMultiTile || p);
+        const int depth = p ? L.blk : L.k;               // (K1p / K1q: the waves fit one block)
+        tile_w[i] = t ? L.tw : 0;
+        tile_seg[i] = t ? L.seg : 0;
+        waves[i] = t ? golk::tile_waves(depth, L.band, L.tw, L.seg) : 0;
+        block_turns[i] = t ? depth : 0;
+    }
+    return (int)std::min<long long>(c->last_n, 0x7fffffff);
+}
+
+int gol_tile_codes(int32_t *codes, int32_t cap)
+{
+    const int n = (int)std::size(golk::kTileCodes);
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileCodes[i];
+    return n;
+}
+
+int gol_tile_count_codes(int32_t *codes, int32_t cap)
+{
+    const int n = (int)std::size(golk::kTileCountCodes);
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileCountCodes[i];
+    return n;
+}
+
+int gol_tile_persist_codes(int32_t *codes, int32_t cap)
+{
+    const int n = GOL_TOOLS ? (int)std::size(golk::kTilePersistCodes) : 0;   // (tools build)
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTilePersistCodes[i];
+    return n;
+}
+
+int gol_tile_stream_codes(int32_t *codes, int32_t cap)
+{
+    const int n = GOL_TOOLS ? (int)std::size(golk::kTileStreamCodes) : 0;   // (tools build)
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileStreamCodes[i];
+    return n;
+}
+
+int gol_step_overlap(gol_ctx *c, int64_t turns, void *recv_stream)
+{
+    if (!c || turns < 0 || !recv_stream) return GOL_EINVAL;
+    std::unique_lock<std::recursive_mutex> lk(c->mu);
+    if (!is_strip(c)) return fail(c, GOL_ESTATE, "not a strip engine");
+    c->halo_valid = c->cfg.halo;   // the receives queued on recv_stream refresh the halos
+    return step_impl(c, turns, (hipStream_t)recv_stream, lk);
+}
+
+int gol_stream_wait(gol_ctx *c, void *stream)
+{
+    if (!c || !stream) return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    HIP_OR_FAIL(c, hipEventRecord(c->ev_main, c->stream));
+    HIP_OR_FAIL(c, hipStreamWaitEvent((hipStream_t)stream, c->ev_main, 0));
+    return GOL_OK;
+}
+
+int gol_set_control(gol_ctx *c, int32_t word)
+{
+    if (!c || word < GOL_CONTROL_RUN || word > GOL_CONTROL_STOP) return GOL_EINVAL;
+    c->control_used.store(true);
+    c->control.store(word);
+    return GOL_OK;
+}
+
+int gol_get_progress(gol_ctx *c, int64_t *turn, int32_t *parked)
+{
+    if (!c) return GOL_EINVAL;
+    if (turn) *turn = c->progress.load();
+    if (parked) *parked = c->parked.load() ? 1 : 0;
+    return GOL_OK;
+}
+
+}  // extern "C"

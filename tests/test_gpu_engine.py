@@ -1041,6 +1041,37 @@ def test_small_board_default_is_tile(gol, oracle, w, h):
     assert np.array_equal(got, oracle.bit_run(start, w, 45))
 
 
+@pytest.mark.parametrize("case", ["torus", "counts", "strip"])
+def test_tune_cache_second_engine_matches_first(gol, oracle, case):
+    """The create-time tune cache: a second engine of the same unpinned shape in one process
+    takes the launch shape the first one measured -- the same gol_info, the same launches at
+    the same tile shapes -- and both stay bit-exact (per-turn counts included)."""
+    w, h = 1024, 96
+    start = oracle.gen_random(w + h, w, h)
+    kw, turns, rows = {}, 45, slice(0, h)
+    if case == "counts":
+        kw = dict(count_every_turn=True)
+    if case == "strip":
+        kw, turns, rows = dict(row_offset=24, rows=48, halo=16), 16, slice(24, 72)
+    want, wc = oracle.bit_run(start, w, turns, counts=True)
+    seen = []
+    for _ in range(2):                               # one after the other: each alone on the device
+        with _engine(gol, w, h, **kw) as e:
+            if case == "strip":
+                e.load_packed(start[np.arange(24 - 16, 72 + 16) % h])
+            else:
+                e.load_packed(start)
+            e.step(turns)
+            i = e.info()
+            seen.append(((i.turns_per_launch, i.band_rows, i.shape_source), e.last_launches(),
+                         e.last_launch_tiles(blocks=True)))
+            assert np.array_equal(e.read_packed(), want[rows])
+            if case == "counts":
+                assert e.turn_counts(1, turns).tolist() == wc.astype(np.int64).tolist()
+    assert seen[0][0][2] == 1 and seen[0][1]
+    assert seen[1] == seen[0]
+
+
 # ------------------------------------------------------- product / tools split
 @pytest.mark.parametrize("mv", [0, 1, 2, 3, 4, 5, 6, 10, 11, 101, 104])
 def test_product_rejects_tools_kernels(gol, monkeypatch, mv):
