@@ -263,7 +263,24 @@ bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg);
 int tile_waves(int turns, int tile_h, int tile_w, int seg);
 // resident workgroups per CU of that launch (occupancy API: VGPRs, LDS; 0 on error)
 int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg);
-long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg);
+// The tiles of one k_step_tile launch over `rows` rows of nw words.  A row's lane columns
+// make ntx = ceil(nl / tile_w) tile columns; when the last one is ragged (r < tile_w lanes)
+// and packs more row segments into a wave at its own width (G' = 64 / (r + 2) > G), it is cut
+// into n_narrow tiles of narrow_w = r lanes x narrow_h rows of its own -- the workgroup size
+// is the launch's, so such a tile holds waves x G' x SEG - 2 turns rows -- instead of nty_main
+// full-price tiles: tiles [0, ntx_main x nty_main) are the full-width ones (ntx_main = ntx - 1
+// columns), the rest the narrow column's, top to bottom.  No repack (n_narrow = 0, ntx_main =
+// ntx): r = tile_w, G' = G, no fewer workgroups, ORD 3 / 7 / 8 / 9, or GOL_TILE_REPACK=0 in
+// the environment (A/B runs; read at every call).
+struct TileGrid {
+    int ntx_main, nty_main;
+    int n_narrow, narrow_w, narrow_h;
+    long long tiles() const { return (long long)ntx_main * nty_main + n_narrow; }
+};
+TileGrid tile_grid(int nw, int rows, int turns, int tile_h, int tile_w, int seg);
+// workgroups of a plain launch of `turns` turns (tile_grid); turns = 0: the rectangular grid
+// ntx x nty of the resident kernels (K1p / K1q / K1r find their neighbours by tile index)
+long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg, int turns = 0);
 hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s);
 // K1p k_tile_persist (gol_tile.h): `turns` turns in blocks of K on tiles resident for the whole
 // launch, exchanging borders between blocks through u0 / u1 (uncached, board-sized) and

@@ -636,6 +636,20 @@ int gol_tile_codes(int32_t *codes, int32_t cap)
     return n;
 }
 
+int gol_tile_grid(int32_t nw, int32_t rows, int32_t turns, int32_t tile_h, int32_t tile_w,
+                  int32_t seg, int32_t *grid)
+{
+    if (!grid || nw < 1 || rows < 1 || !golk::tile_shape_ok(nw, turns, tile_h, tile_w, seg))
+        return GOL_EINVAL;
+    const golk::TileGrid g = golk::tile_grid(nw, rows, turns, tile_h, tile_w, seg);
+    grid[0] = g.ntx_main;
+    grid[1] = g.nty_main;
+    grid[2] = g.n_narrow;
+    grid[3] = g.narrow_w;
+    grid[4] = g.narrow_h;
+    return GOL_OK;
+}
+
 int gol_tile_count_codes(int32_t *codes, int32_t cap)
 {
     const int n = (int)std::size(golk::kTileCountCodes);

@@ -132,6 +132,60 @@ constexpr size_t tile_lds_bytes_code(int threads, int code)
                                        : tile_lds_bytes(threads, tile_seg_words(code));
 }
 
+// lane / C for lane < 64 as a multiply and a shift: rcp = ceil(65536 / C), exact for every
+// C = 3 .. 64 (checked below), so no kernel divides by a tile's width
+constexpr uint32_t tile_rcp16(int c) { return (65536u + (uint32_t)c - 1u) / (uint32_t)c; }
+constexpr bool tile_rcp16_exact()
+{
+    for (int c = 3; c <= 64; ++c)
+        for (uint32_t l = 0; l < 64; ++l)
+            if (((l * tile_rcp16(c)) >> 16) != l / (uint32_t)c) return false;
+    return true;
+}
+static_assert(tile_rcp16_exact(), "lane * ceil(65536 / C) >> 16 == lane / C below 64");
+
+// One tile of a launch, wave-uniform: its width in lanes and height in rows, its first lane
+// column and buffer row, the row segments a wave holds side by side (64 / (tw + 2)) and
+// tile_rcp16(tw + 2).  The tiles of one launch need not be alike (golk::tile_grid: the narrow
+// last column); everything tile_pass does is expressed in these values.
+struct TilePos {
+    int tw, th, x0, y0, g;
+    uint32_t rcp;
+};
+// tile `tile` of the rectangular grid of ntx columns (the resident kernels)
+__device__ __forceinline__ TilePos tile_pos_rect(const StepArgs &a, int tile, int ntx)
+{
+    const int ty = tile / ntx, tx = tile - ty * ntx;
+    const int c = a.tile_w + 2;
+    return TilePos{a.tile_w, a.band, tx * a.tile_w, a.row_lo + ty * a.band, 64 / c, tile_rcp16(c)};
+}
+// One launch's tiles as k_step_tile / k_step_tile_cnt take them (launch_tile fills this from
+// golk::tile_grid): tiles [0, n_main) are tile_w x band, ntx_main to a tile row; tiles
+// [n_main, ntiles) are the narrow column's, narrow_w x narrow_h, at lane column ntx_main x
+// tile_w.  Index 0 of g / rcp: the main tiles, 1: the narrow ones.
+struct TileLaunch {
+    int ntiles, n_main, ntx_main;
+    uint32_t inv_ntx;           // floor(2^32 / ntx_main) + 1 (ntx_main >= 2; else unused)
+    int narrow_w, narrow_h;
+    int g[2];
+    uint32_t rcp[2];
+};
+// (blockIdx-derived: the split stays on the scalar unit)
+__device__ __forceinline__ TilePos tile_pos(const StepArgs &a, const TileLaunch &L, int tile)
+{
+    if (tile >= L.n_main)
+        return TilePos{L.narrow_w, L.narrow_h, L.ntx_main * a.tile_w,
+                       a.row_lo + (tile - L.n_main) * L.narrow_h, L.g[1], L.rcp[1]};
+    // tile / ntx_main by the host's reciprocal: the estimate is the quotient or one more
+    int ty = tile;
+    if (L.ntx_main > 1) {
+        ty = (int)__umulhi((uint32_t)tile, L.inv_ntx);
+        ty -= ty * L.ntx_main > tile ? 1 : 0;
+    }
+    const int tx = tile - ty * L.ntx_main;
+    return TilePos{a.tile_w, a.band, tx * a.tile_w, a.row_lo + ty * a.band, L.g[0], L.rcp[0]};
+}
+
 // W words per lane (2W dwords, interleaved layout word by word).  With W = 2 the lane's two
 // words are neighbours, so only the outer edges need a lane shift: per row 2 DPP + 2W funnel
 // shifts + 4W v_bitop3 instead of W x (2 + 2 + 4) -- 48 instead of 52 SIMD cycles per 4096
@@ -145,6 +199,7 @@ constexpr size_t tile_lds_bytes_code(int threads, int code)
 // K1r (RING): the tile stays in registers across blocks; between blocks only its ring is
 // exchanged (k_tile_ring below)
 struct RingArgs {
+    int tile, ntx;              // the tile's index in the rectangular grid of ntx columns
     uint64_t *u0, *u1;          // board-layout edge buffers, block b writes u[b % 2]
     unsigned *flags;            // per tile: epoch + b + 1 once its block-b edges are stored
     unsigned epoch;
@@ -168,7 +223,7 @@ struct RingArgs {
 template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false>
 __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                                           uint64_t *__restrict__ out, const StepArgs &a,
-                                          int turns, int tile, int ntx,
+                                          int turns, const TilePos &pos,
                                           RingArgs ra = RingArgs{})
 {
     constexpr int ND = 2 * W;                            // dwords per lane and row
@@ -178,15 +233,14 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     // segment-major, C slots per segment (dynamic LDS, W uint4 per slot)
     extern __shared__ uint4 xsh[];
     const int nslot = (int)(blockDim.x);                 // waves x 64 >= segments x C
-    const int TW = a.tile_w, C = TW + 2, G = 64 / C;     // (in lanes of W words)
-    const int K = turns, TH = a.band;
+    const int TW = pos.tw, C = TW + 2, G = pos.g;        // (in lanes of W words)
+    const int K = turns, TH = pos.th;
     const int nl = a.nw / W;                             // lane columns per row
-    const int ty = tile / ntx, tx = tile - ty * ntx;
-    const int y0 = a.row_lo + ty * TH;
-    const int x0 = tx * TW;
+    const int y0 = pos.y0;
+    const int x0 = pos.x0;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int group = lane / C, col = lane - group * C;
+    const int group = (int)(((uint32_t)lane * pos.rcp) >> 16), col = lane - group * C;
     const bool live = group < G;                         // lanes past G groups: idle
     const int nseg = (TH + 2 * K + SEG - 1) / SEG;       // segments the tile needs
     // ORD 7 (G == 2, nseg >= 3; host-checked): wave 0 holds the top segment (group 0) and the
@@ -205,15 +259,32 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
 
     // lane column (torus wrap) and the lane's rows: tile row t = seg * SEG + i is buffer row
     // y0 - K + t (mod modrows; rows past the tile are read, never stored)
+    // (gx lies in [-1, nl + C - 2): one wrap either way unless the row is narrower than the
+    // tile -- a wave-uniform case)
     int gx = x0 - 1 + (live ? col : 0);
-    while (gx < 0) gx += nl;
-    while (gx >= nl) gx -= nl;
+    if (nl < C) {
+        while (gx < 0) gx += nl;
+        while (gx >= nl) gx -= nl;
+    } else {
+        gx += gx < 0 ? nl : 0;
+        gx -= gx >= nl ? nl : 0;
+    }
     const int M = a.modrows;
     const uint32_t pitch_b = (uint32_t)a.pitch * 8u;
     const uint32_t span = (uint32_t)M * pitch_b;
-    int r = y0 - K + (live ? seg : 0) * SEG + (rev ? SEG - 1 : 0);
-    while (r < 0) r += M;
-    while (r >= M) r -= M;
+    // the tile's first row wraps on the scalar unit; the lane's segment then starts less than
+    // 2 M rows down unless the buffer is shorter than the workgroup's rows (one ballot)
+    int rbase = y0 - K;                                  // (>= -K, < M)
+    if (rbase < 0) {
+        rbase += M;
+        while (rbase < 0) rbase += M;                    // (a buffer of fewer than K rows)
+    }
+    int r = rbase + (live ? seg : 0) * SEG + (rev ? SEG - 1 : 0);
+    if (__builtin_amdgcn_ballot_w64(r >= 2 * M) != 0) {
+        while (r >= M) r -= M;
+    } else {
+        r -= r >= M ? M : 0;
+    }
     uint32_t off = (uint32_t)r * pitch_b + (uint32_t)gx * (8u * W);
     [[maybe_unused]] const uint32_t off_first = off;     // (RING: the segment's first row)
     const uint32_t lstep = rev ? span - pitch_b : pitch_b;   // (a reversed segment loads upwards)
@@ -227,21 +298,32 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     // by another CU's stores
     constexpr int kLoadAux = PERSIST ? 16 : GOL_TILE_LOAD_AUX;
     uint32_t v[SEG][ND];
-#pragma unroll
-    for (int i = 0; i < SEG; ++i) {
+    auto load_row = [&](int i, uint32_t voff, uint32_t soff) {
         if constexpr (W == 1) {
-            const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rin, off, 0, kLoadAux);
+            const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rin, voff, soff, kLoadAux);
             v[i][0] = w.x;
             v[i][1] = w.y;
         } else {
-            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rin, off, 0, kLoadAux);
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rin, voff, soff, kLoadAux);
             v[i][0] = w.x;
             v[i][1] = w.y;
             v[i][2] = w.z;
             v[i][3] = w.w;
         }
-        off += lstep;
-        off = off >= span ? off - span : off;            // (the column stays < pitch_b)
+    };
+    // No segment of the wave wraps past the buffer's last row inside its SEG rows (one ballot;
+    // nearly every wave): one lane offset, the rows stepped by the scalar offset of the buffer
+    // instruction -- no VALU per row.  Otherwise the offset wraps row by row.
+    if (!kHalo && __builtin_amdgcn_ballot_w64(r + SEG > M) == 0) {
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) load_row(i, off, (uint32_t)i * pitch_b);
+    } else {
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            load_row(i, off, 0);
+            off += lstep;
+            off = off >= span ? off - span : off;        // (the column stays < pitch_b)
+        }
     }
 
     // 3-cell row sums of one row: per word w (even dword e, odd dword o) the sums of the even
@@ -337,8 +419,11 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     // workgroup barrier no longer counts it once it has ended.
     // the wave's tile rows (ORD 7: wave 0 spans the whole tile -- it never leaves; wave w > 0
     // holds segments (w - 1) G + 1 ..)
-    const int wrow0 = !kHalo ? wave * G * SEG : wave == 0 ? 0 : ((wave - 1) * G + 1) * SEG;
-    const int wrow1 = !kHalo ? wrow0 + G * SEG : wave == 0 ? 1 << 30 : wrow0 + G * SEG;
+    // (both through readfirstlane: the leave test of the turn loop stays on the scalar unit)
+    const int wrow0 = __builtin_amdgcn_readfirstlane(
+        !kHalo ? wave * G * SEG : wave == 0 ? 0 : ((wave - 1) * G + 1) * SEG);
+    const int wrow1 = __builtin_amdgcn_readfirstlane(
+        !kHalo ? wrow0 + G * SEG : wave == 0 ? 1 << 30 : wrow0 + G * SEG);
     // ORD 4: per-wave progress flags after the slot arrays.  flag[w] = the last turn whose
     // edge sums wave w has published (-1 before the first; INT_MAX once it has left), written
     // by lane 0 after its sums: the LDS serves one wave's requests in issue order, so a wave
@@ -649,6 +734,7 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         static_assert(PERSIST && W == 1 && ORD != 4 && ORD != 7 && ORD < 8, "K1r: one word per lane");
         const int THv = min(TH, a.row_hi - y0), TWv = min(TW, nl - x0);
         const int nty = (a.row_hi - a.row_lo + TH - 1) / TH;
+        const int tile = ra.tile, ntx = ra.ntx, ty = tile / ntx, tx = tile - ty * ntx;
         const int nblocks = (ra.turns + K - 1) / K, kbase = ra.turns / nblocks,
                   kextra = ra.turns % nblocks;
         bool gave_up = false;
@@ -673,7 +759,7 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
             int ln = lane, thv = THv, twv = TWv, kk = K;
             uint32_t off0 = off_first;
             asm volatile("" : "+v"(ln), "+v"(off0), "+s"(thv), "+s"(twv), "+s"(kk));
-            const int gr = ln / C, cl = ln - gr * C;
+            const int gr = (int)(((uint32_t)ln * pos.rcp) >> 16), cl = ln - gr * C;
             const bool lv = gr < G;
             const int tr0 = (wave * G + gr) * SEG;       // the lane's first tile row
             if (lv && cl >= 1 && cl <= twv && !(ra.ablate & 1)) {
@@ -790,7 +876,7 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         uint32_t all = ~0u;
         asm volatile("" : "+v"(all));
         const int ln = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
-        const int gr = ln / C, cl = ln - gr * C;
+        const int gr = (int)(((uint32_t)ln * pos.rcp) >> 16), cl = ln - gr * C;
         if (gr >= G || cl < 1 || cl > TW || x0 + cl - 1 >= nl) return;
         const int t0 = (wave * G + gr) * SEG;
         uint32_t so = (uint32_t)(y0 - K + t0) * pitch_b + (uint32_t)(x0 + cl - 1) * 8u;
@@ -813,8 +899,10 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
             turn(std::integral_constant<int, 0>{}, (t & 1) * 2 * nslot, t);
         }
     } else if constexpr (!kPairs) {
+        // (the second leave test as one scalar, formed once: t > lastrow - wrow0)
+        const int tlast = __builtin_amdgcn_readfirstlane(lastrow - wrow0);
         for (int t = 0; t < K; ++t) {
-            if (!PERSIST && (wrow1 <= t || wrow0 > lastrow - t)) {   // (wave-uniform)
+            if (!PERSIST && (wrow1 <= t || t > tlast)) {         // (wave-uniform)
                 leave(t);
                 gone = true;
                 break;
@@ -858,7 +946,50 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         }
     }
     // interior rows [K, K + TH) of the tile, below row_hi; interior columns inside the row
-    if (gone || !live || col < 1 || col > TW || x0 + col - 1 >= nl) return;
+    if (gone) return;
+    auto store_row = [&](int i, uint32_t voff, uint32_t soff) {
+        if constexpr (W == 1 && GOL_TILE_STORE_AUX != 0) {
+            const u32x2 d = {v[i][0], v[i][1]};
+            __builtin_amdgcn_raw_buffer_store_b64(d, rout, voff, soff, GOL_TILE_STORE_AUX);
+        } else {
+            buf_store(v[i], rout, voff, soff);
+        }
+    };
+    if constexpr (!kHalo) {
+        // the lane's stored local rows [lo, hi): tile rows [K, K + TH) below row_hi
+        // (the lane's column and segment formed again here, from the lane count of an opaque
+        // mask: nothing of the store stage stays live across the turns -- 2 VGPRs less)
+        uint32_t all = ~0u;
+        asm volatile("" : "+v"(all));
+        const int sl = (int)__builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+        const int sg = (int)(((uint32_t)sl * pos.rcp) >> 16), sc = sl - sg * C;
+        const bool scol = sg < G && sc >= 1 && sc <= TW && x0 + sc - 1 < nl;
+        const int t0 = (wave * G + sg) * SEG;
+        const int top = min(K + TH, a.row_hi - (y0 - K));    // (wave-uniform)
+        const int lo = min(max(K - t0, 0), SEG), hi = min(max(top - t0, 0), SEG);
+        uint32_t so = (uint32_t)(y0 - K + t0) * pitch_b + (uint32_t)(x0 + sc - 1) * (8u * W);
+        // Every storing lane of the wave stores its whole segment (one ballot; every wave but
+        // the tile's first and last, and the board's last tile row): all SEG rows under one
+        // exec mask, stepped by the instruction's scalar offset.  The lane's offset is that of
+        // a stored row, inside the buffer (the range check sees it without the scalar part).
+        if (__builtin_amdgcn_ballot_w64(scol && (lo > 0 || hi < SEG)) == 0) {
+            if (scol) {
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) store_row(i, so, (uint32_t)i * pitch_b);
+            }
+            return;
+        }
+        // a wave at the tile's edge: a row range per lane (the offset may start above row 0
+        // and is exact once inside the stored rows, so it steps in the lane's register)
+        if (!scol || hi <= lo) return;
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            if (i >= lo && i < hi) store_row(i, so, 0);
+            so += pitch_b;
+        }
+        return;
+    }
+    if (!live || col < 1 || col > TW || x0 + col - 1 >= nl) return;
     const int t0 = seg * SEG + (rev ? SEG - 1 : 0);
     const int dr = rev ? -1 : 1;
     const uint32_t sstep = rev ? 0u - pitch_b : pitch_b;
@@ -1094,11 +1225,11 @@ __device__ __forceinline__ int tile_of_block(int ntiles)
 template <int SEG, int ORD, int W>
 __global__ __launch_bounds__(1024, (ORD == 7 ? 6 : 1)) void k_step_tile(const uint64_t *__restrict__ in,
                                                      uint64_t *__restrict__ out, StepArgs a,
-                                                     int turns, int ntx, int ntiles)
+                                                     int turns, TileLaunch L)
 {
-    const int tile = tile_of_block(ntiles);
-    if (tile >= ntiles) return;                          // the whole workgroup
-    tile_pass<SEG, ORD, W, false>(in, out, a, turns, tile, ntx);
+    const int tile = tile_of_block(L.ntiles);
+    if (tile >= L.ntiles) return;                        // the whole workgroup
+    tile_pass<SEG, ORD, W, false>(in, out, a, turns, tile_pos(a, L, tile));
 }
 
 // k_step_tile with the per-turn alive counts fused (tile_pass CNT; the instantiations:
@@ -1106,11 +1237,11 @@ __global__ __launch_bounds__(1024, (ORD == 7 ? 6 : 1)) void k_step_tile(const ui
 template <int SEG, int ORD, int W>
 __global__ __launch_bounds__(1024, 1) void k_step_tile_cnt(const uint64_t *__restrict__ in,
                                                            uint64_t *__restrict__ out, StepArgs a,
-                                                           int turns, int ntx, int ntiles)
+                                                           int turns, TileLaunch L)
 {
-    const int tile = tile_of_block(ntiles);
-    if (tile >= ntiles) return;                          // the whole workgroup
-    tile_pass<SEG, ORD, W, false, false, true>(in, out, a, turns, tile, ntx);
+    const int tile = tile_of_block(L.ntiles);
+    if (tile >= L.ntiles) return;                        // the whole workgroup
+    tile_pass<SEG, ORD, W, false, false, true>(in, out, a, turns, tile_pos(a, L, tile));
 }
 
 // ORD 3: tile pairs (tile_pass_pair).  Pair j runs tiles 2j and 2j + 1; with an odd count the
@@ -1174,7 +1305,7 @@ __global__ __launch_bounds__(1024, 1) void k_tile_persist(
         }
         const uint64_t *src = b == 0 ? in : ((b & 1) ? u0 : u1);
         uint64_t *dst = b + 1 == nblocks ? out : ((b & 1) ? u1 : u0);
-        tile_pass<SEG, ORD, W, true>(src, dst, a, k, tile, ntx);
+        tile_pass<SEG, ORD, W, true>(src, dst, a, k, tile_pos_rect(a, tile, ntx));
         if (b + 1 == nblocks) break;
         __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8));   // this wave's stores are done
         __syncthreads();                                     // ... and every wave's
@@ -1201,8 +1332,9 @@ __global__ __launch_bounds__(1024, 1) void k_tile_ring(
 {
     const int tile = tile_of_block(ntiles);
     if (tile >= ntiles) return;                          // (never waited for)
-    tile_pass<SEG, ORD, 1, true, true>(in, out, a, K, tile, ntx,
-                                       RingArgs{u0, u1, flags, epoch, turns, gcount, gbase, ablate});
+    tile_pass<SEG, ORD, 1, true, true>(in, out, a, K, tile_pos_rect(a, tile, ntx),
+                                       RingArgs{tile, ntx, u0, u1, flags, epoch, turns, gcount, gbase,
+                                                ablate});
 }
 
 // K1q k_tile_stream: K1p's blocks for boards whose tiles do not all fit at once.  One launch
@@ -1285,7 +1417,7 @@ __global__ __launch_bounds__(1024, (SEG >= 20 ? 6 : 8)) void k_tile_stream(
         StepArgs aa = a;
         asm volatile("" : "+s"(aa.tile_w), "+s"(aa.band), "+s"(aa.nw), "+s"(aa.pitch),
                      "+s"(aa.modrows));
-        tile_pass<SEG, ORD, W, true>(src, dst, aa, k, tile, ntx);
+        tile_pass<SEG, ORD, W, true>(src, dst, aa, k, tile_pos_rect(aa, tile, ntx));
         if (b + 1 < nblocks) {
             __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8));   // this wave's stores are done
             __syncthreads();                                     // ... and every wave's

@@ -264,8 +264,42 @@ int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg)
     return blocks;
 }
 
-long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg)
+TileGrid tile_grid(int nw, int rows, int turns, int tile_h, int tile_w, int seg)
 {
+    TileGrid g{0, 0, 0, 0, 0};
+    if (nw < 1 || rows < 1 || tile_h < 1 || tile_w < 1 || tile_w + 2 > 64) return g;
+    const int nl = nw / tile_seg_words(seg);
+    const int ntx = (nl + tile_w - 1) / tile_w;
+    g.ntx_main = ntx;
+    g.nty_main = (rows + tile_h - 1) / tile_h;
+    const int ord = seg / 100 % 10, segrows = seg % 100;
+    // (ORD 7's wave 0 holds two lane groups by construction, ORD 8 / 9 and the ORD 3 forms
+    // are tools-build experiments: they keep the rectangular grid)
+    if (turns < 1 || segrows < 1 || ord == 3 || ord >= 7) return g;
+    const char *env = getenv("GOL_TILE_REPACK");
+    if (env && atoi(env) == 0) return g;
+    const int r = nl - (ntx - 1) * tile_w;               // lanes of the last tile column
+    if (r <= 0 || r >= tile_w) return g;
+    const int G = 64 / (tile_w + 2), Gn = 64 / (r + 2);
+    if (Gn <= G) return g;
+    // blockDim is launch-uniform: the narrow tiles have the main tiles' waves
+    const int waves = tile_waves(turns, tile_h, tile_w, seg);
+    if (waves < 1 || waves > kTileMaxWaves) return g;
+    const long long hmax = (long long)waves * Gn * segrows - 2 * turns;
+    if (hmax < 1) return g;
+    const long long n = (rows + hmax - 1) / hmax;
+    if (n >= g.nty_main) return g;
+    g.ntx_main = ntx - 1;
+    g.n_narrow = (int)n;
+    g.narrow_w = r;
+    // evened out over the n tiles: the last one is no sliver
+    g.narrow_h = (int)std::min<long long>((rows + n - 1) / n, rows);
+    return g;
+}
+
+long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg, int turns)
+{
+    if (turns > 0) return tile_grid(nw, rows, turns, tile_h, tile_w, seg).tiles();
     const long long nl = nw / tile_seg_words(seg);
     const long long ntx = (nl + tile_w - 1) / tile_w;
     return ntx * ((rows + tile_h - 1) / tile_h);
@@ -275,9 +309,22 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
 {
     const int rows = a.row_hi - a.row_lo;
     if (!tile_shape_ok(a.nw, turns, a.band, a.tile_w, a.tile_seg)) return hipErrorInvalidValue;
-    const int ntx = (a.nw / tile_seg_words(a.tile_seg) + a.tile_w - 1) / a.tile_w;
-    const long long ntiles = (long long)ntx * ((rows + a.band - 1) / a.band);
+    // (ORD 3 with GOL_TILE_PAIR pairs tiles by index: tile_grid leaves its grid rectangular)
+    const TileGrid g = tile_grid(a.nw, rows, turns, a.band, a.tile_w, a.tile_seg);
+    const int ntx = g.ntx_main;
+    const long long ntiles = g.tiles();
     if (ntiles <= 0 || ntiles > (1 << 24)) return hipErrorInvalidValue;
+    TileLaunch L{};
+    L.ntiles = (int)ntiles;
+    L.n_main = g.ntx_main * g.nty_main;
+    L.ntx_main = g.ntx_main;
+    L.inv_ntx = g.ntx_main > 1 ? (uint32_t)((1ull << 32) / (unsigned)g.ntx_main) + 1u : 0u;
+    L.narrow_w = g.narrow_w;
+    L.narrow_h = g.narrow_h;
+    L.g[0] = 64 / (a.tile_w + 2);
+    L.rcp[0] = tile_rcp16(a.tile_w + 2);
+    L.g[1] = g.n_narrow ? 64 / (g.narrow_w + 2) : L.g[0];
+    L.rcp[1] = g.n_narrow ? tile_rcp16(g.narrow_w + 2) : L.rcp[0];
     // (ORD 3 with GOL_TILE_PAIR: one workgroup per pair of tiles)
     const long long units = GOL_TILE_PAIR && a.tile_seg / 100 == 3 ? (ntiles + 1) / 2 : ntiles;
     const unsigned blocks = (unsigned)((units + 7) / 8 * 8);
@@ -291,8 +338,11 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
     const uint64_t *in = a.in;
     uint64_t *out = a.out;
     int k = turns, ntx_arg = ntx, nt = (int)ntiles;
-    void *params[] = {&in, &out, &args, &k, &ntx_arg, &nt};
-    return hipLaunchKernel(fn, dim3(blocks), dim3(threads), params,
+    // (k_step_tile_pair keeps the rectangular grid's arguments)
+    void *params_pair[] = {&in, &out, &args, &k, &ntx_arg, &nt};
+    void *params[] = {&in, &out, &args, &k, &L};
+    return hipLaunchKernel(fn, dim3(blocks), dim3(threads),
+                           GOL_TILE_PAIR && a.tile_seg / 100 == 3 ? params_pair : params,
                            tile_lds_bytes_code(threads, a.tile_seg) + (a.counts ? tile_count_lds_bytes(threads) : 0),
                            s);
 }

@@ -59,7 +59,7 @@ constexpr bool all_shipped(const int (&codes)[N])
 double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg)
 {
     if (!golk::tile_shape_ok(nw, K, th, tw, seg)) return 0;
-    const long long tiles = golk::tile_count(nw, rows, th, tw, seg);
+    const long long tiles = golk::tile_count(nw, rows, th, tw, seg, K);   // (what is launched)
     const int waves = golk::tile_waves(K, th, tw, seg);
     const int wgpc = golk::tile_blocks_per_cu(K, th, tw, seg);         // VGPRs, LDS
     if (wgpc <= 0) return 0;

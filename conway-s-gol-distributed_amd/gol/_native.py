@@ -125,6 +125,7 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "gol_tile_grid": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int32)]),
     "gol_tile_count_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_persist_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_stream_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),

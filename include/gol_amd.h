@@ -189,6 +189,14 @@ int gol_last_launch_tiles(gol_ctx *ctx, int32_t *tile_w, int32_t *tile_seg, int3
  * tests: every code the shape search can pick has an oracle test).  Writes min(n, cap) codes,
  * returns n.  Needs no device. */
 int gol_tile_codes(int32_t *codes, int32_t cap);
+/* The workgroups of one k_step_tile launch of `turns` turns over `rows` rows of nw words, on
+ * tiles of tile_h rows x tile_w lanes with segment code seg: grid[0] x grid[1] full-width
+ * tiles (columns x rows) and, when the ragged last tile column is repacked at its own width,
+ * grid[2] narrow tiles of grid[3] lanes x grid[4] rows in its place (else grid[2..4] = 0 and
+ * grid[0] counts every column).  GOL_TILE_REPACK=0 in the environment turns the repack off.
+ * Needs no device.  GOL_EINVAL for a shape the library does not run. */
+int gol_tile_grid(int32_t nw, int32_t rows, int32_t turns, int32_t tile_h, int32_t tile_w,
+                  int32_t seg, int32_t *grid);
 /* The subset with a counted form (k_step_tile with the per-turn alive counts fused): the codes
  * a GOL_FLAG_COUNT_EVERY_TURN engine runs multi-turn launches on; same convention. */
 int gol_tile_count_codes(int32_t *codes, int32_t cap);
