@@ -125,6 +125,11 @@ struct gol_ctx {
     int device = 0;
     int nw = 0, pitch = 0, buf_rows = 0;
     bool fast = false;
+    // a width of >= 256 cells that is no multiple of 128 (a partial last word, or an odd word
+    // count): multi-turn launches on k_step_tile alone, one word per lane -- across the row seam
+    // at a golk::kTileSeamCodes code when width % 64 != 0.  (Off for forced-generic and count
+    // engines, and under a GOL_MULTI_VARIANT other than k_step_tile: one turn per launch.)
+    bool tile_only = false;
     int band = 8;
     int variant = golk::kVariantDefault;
     int multi_words = 2;                     // k_step_multi words per lane
@@ -314,8 +319,10 @@ struct TileShape {
     int K = 0, th = 0, tw = 0, seg = 0;
     double model_us = 0;                     // modelled time per turn
 };
-double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg);
-std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt = false);
+// (width: the board's when its width is no multiple of 64 -- golk::tile_shape_ok; else 0)
+double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg, int width = 0);
+std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt = false,
+                                       int width = 0);
 // the engine runs k_step_tile at this shape (no plan, no K1p; K1q's shape and the measured time
 // stay)
 void apply_tile(gol_ctx *c, const TileShape &t);

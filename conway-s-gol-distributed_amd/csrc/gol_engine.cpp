@@ -304,7 +304,8 @@ int initial_tile_shape(gol_ctx *c, bool cntb)
     int K = cfg->turns_per_launch > 0 ? std::min(cfg->turns_per_launch, golk::kMaxTileTurns) : 0;
     if (const char *v = getenv("GOL_TURNS_PER_LAUNCH"))
         K = std::max(2, std::min(atoi(v), golk::kMaxTileTurns));
-    std::vector<TileShape> cand = tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20, cntb);
+    std::vector<TileShape> cand =
+        tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20, cntb, c->cfg.width);
     for (const TileShape &t : cand)
         if (K == 0 || t.K == K) {
             apply_tile(c, t);
@@ -314,7 +315,8 @@ int initial_tile_shape(gol_ctx *c, bool cntb)
         // no ranked shape at this depth (K not in the candidate list): best TW / TH at K
         TileShape best;
         for (const TileShape &t : cand) {
-            const double m = tile_model_us(c->ncu, c->nw, c->buf_rows, K, t.th, t.tw, t.seg);
+            const double m =
+                tile_model_us(c->ncu, c->nw, c->buf_rows, K, t.th, t.tw, t.seg, c->cfg.width);
             if (m > 0 && (best.K == 0 || m < best.model_us)) best = {K, t.th, t.tw, t.seg, m};
         }
         if (best.K) apply_tile(c, best);
@@ -330,9 +332,11 @@ int initial_tile_shape(gol_ctx *c, bool cntb)
         }
     }
     if (s.multi_variant == golk::kMultiTile &&
-        !golk::tile_shape_ok(c->nw, s.tpl, s.band_multi, s.tile_w, s.tile_seg))
+        !golk::tile_shape_ok(c->nw, s.tpl, s.band_multi, s.tile_w, s.tile_seg, c->cfg.width))
         return GOL_EINVAL;
-    return blocks_parse_env(c);              // GOL_PERSIST / GOL_RING / GOL_STREAM
+    if (int rc = blocks_parse_env(c)) return rc;   // GOL_PERSIST / GOL_RING / GOL_STREAM
+    // (K1p / K1q / K1r know nothing of the row seam or of odd word counts)
+    return c->tile_only && (s.persist_k > 0 || s.stream_k > 0) ? GOL_EINVAL : GOL_OK;
 }
 
 }  // namespace
@@ -415,6 +419,11 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
             c->wg_prio |= (unsigned)(v[w] - '0') << (2 * w);
         if (!c->wg_prio) c->wg_prio = 0x100;              // all zero: still an override
     }
+    // widths of >= 256 cells that are no multiple of 128: K1t alone blocks them (count engines:
+    // it has no counted form across the seam, and they keep one rule at all these widths)
+    c->tile_only = !golk::fast_path_ok(cfg->width) && cfg->width >= 256 && c->multi_words == 1 &&
+                   !(cfg->flags & (GOL_FLAG_FORCE_GENERIC | GOL_FLAG_COUNT_EVERY_TURN));
+    if (c->tile_only) s.multi_variant = golk::kMultiTile;
     if (const char *v = getenv("GOL_MULTI_VARIANT")) {    // A/B experiments only
         const int k = atoi(v);
         const bool known = (k >= 0 && k < golk::kMultiUserEnd) || k > golk::kMultiAblate;
@@ -426,7 +435,9 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
             return GOL_EINVAL;
         }
         s.multi_variant = k;
+        if (k != golk::kMultiTile) c->tile_only = false;   // (no other kernel runs these widths)
     }
+    const bool blockable = c->fast || c->tile_only;
     const int lane_dw = golk::multi_lane_dwords(c->multi_words, s.multi_variant);
     const int auto_bm = golk::auto_band_multi(cfg->width, cfg->rows, lane_dw);
     const bool wg = golk::is_wg_variant(s.multi_variant);
@@ -434,9 +445,9 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
                                       : (wg ? 16 : (auto_bm >= 48 ? 8 : 6));
     if (const char *v = getenv("GOL_TURNS_PER_LAUNCH")) s.tpl = atoi(v);
     s.tpl = std::max(1, std::min(s.tpl, golk::multi_max_turns(s.multi_variant)));
-    if (c->fast && s.tpl > 1 && !golk::multi_fits(c->nw, c->pitch, c->buf_rows))
+    if (blockable && s.tpl > 1 && !golk::multi_fits(c->nw, c->pitch, c->buf_rows))
         c->blocking_limited = true;   // reported in gol_info.blocking_limited
-    if (!c->fast || c->blocking_limited) s.tpl = 1;
+    if (!blockable || c->blocking_limited) s.tpl = 1;
     c->halo_valid = cfg->halo;
     if (cfg->flags & GOL_FLAG_COUNT_EVERY_TURN) {
         const char *v = getenv("GOL_COUNT_BLOCKING");    // 0: one-turn launches (A/B, probes)
@@ -488,11 +499,21 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     // small boards (and k_step_tile pinned by GOL_MULTI_VARIANT): k_step_tile at the model's
     // best shape for the requested or default depth; the autotune below times the model's best
     // shapes
-    const bool small = c->fast && s.tpl > 1 && (long long)c->buf_rows * c->pitch < (1ll << 20);
+    // (a tile_only engine of any size plans like a small board: k_step_tile, searched)
+    const bool small = blockable && s.tpl > 1 &&
+                       (c->tile_only || (long long)c->buf_rows * c->pitch < (1ll << 20));
     const bool pinned = getenv("GOL_MULTI_VARIANT") != nullptr;
-    if (c->fast && s.tpl > 1 &&
+    if (blockable && s.tpl > 1 &&
         ((small && !pinned && cfg->band_rows <= 0) || s.multi_variant == golk::kMultiTile))
-        if (int rc2 = initial_tile_shape(c, cntb)) return bail(rc2);
+        if (int rc2 = initial_tile_shape(c, cntb)) {
+            // a tile_only board no tile shape fits (a few rows) and nothing pinned: one turn per
+            // launch, as before; every other failure is the caller's shape
+            if (!c->tile_only || pinned || getenv("GOL_TILE") || cfg->band_rows > 0)
+                return bail(rc2);
+            LaunchShape one;
+            one.multi_variant = golk::kMultiTile;
+            set_shape(c, std::move(one));
+        }
     const char *at = getenv("GOL_AUTOTUNE");
     bool tuning = !(cfg->flags & GOL_FLAG_NO_AUTOTUNE) && (!at || atoi(at) != 0) &&
                   cfg->band_rows <= 0 && s.tpl > 1;

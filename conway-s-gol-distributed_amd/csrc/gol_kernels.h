@@ -170,7 +170,9 @@ constexpr bool is_helix_variant(int v)
 {
     return v == kMultiWgHx || v == kMultiWgPg || v == kMultiWgHxS || v == kMultiWgPgS;
 }
-bool multi_ok(int width, int turns, int variant);
+// (k_step_skew / k_step_wg: fast-path widths; kMultiTile: any width >= 256, and with a tile
+// code given, one that runs at that width)
+bool multi_ok(int width, int turns, int variant, int tile_code = 0);
 // waves sharing one band pipeline at depth `turns` (k_step_wg: wg_waves, else 1)
 int multi_waves_per_band(int variant, int turns);
 // band pipelines per thread block (k_step_skew: 4 single-wave pipelines; k_step_wg: 1)
@@ -259,10 +261,90 @@ constexpr bool tile_count_codes_shipped()
     return true;
 }
 static_assert(tile_count_codes_shipped(), "kTileCountCodes: a subset of kTileCodes, W = 1");
-bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg);
+// the codes k_step_tile_seam is instantiated for (gol_tile_seam.hip tile_seam_kernel): K1t on a
+// board whose width is no multiple of 64, where the torus seam in x falls inside the row's last
+// word (tile_pass SEAM, seam_stitch below).  One word per lane, plain launches, no counted form.
+// Every code the shape search picks on such a board (gol_tune.cpp) is one of these: the short
+// segments of the small boards (SEG 2 in both turn orders: what boards of a few thousand words
+// run fastest on), both loop forms (turn pairs up to SEG 12, one body above) and the 80-VGPR
+// ORD 5 family of the large ones.  Each one is pinned by
+// tests/test_gpu_seam.py through gol_tile_seam_codes.
+constexpr int kTileSeamCodes[] = {
+    2,   16,                                                                     // ORD 0
+    102, 104, 106, 108, 112, 116,                                                // ORD 1
+    516, 524,                                                                    // ORD 5
+};
+constexpr bool tile_code_seam(int code)
+{
+    for (int c : kTileSeamCodes)
+        if (c == code) return true;
+    return false;
+}
+constexpr bool tile_seam_codes_shipped()
+{
+    for (int c : kTileSeamCodes)
+        if (!tile_code_shipped(c) || c >= 1000) return false;
+    return true;
+}
+static_assert(tile_seam_codes_shipped(), "kTileSeamCodes: a subset of kTileCodes, W = 1");
+
+// ---- the row seam.  A row of `width` cells, width % 64 = r in 1 .. 63, has nw = L + 1 words;
+// its last word w[L] holds r cells and zero padding (the board invariant).  K1t's lanes hold
+// virtual lane columns: column v = cells 64 v .. 64 v + 63 (mod width), so the columns -1 and
+// >= L are no real word but the stitch of two:
+//     v = -1          (w[L-1] >> r) | (w[L] << (64 - r))
+//     v = L           w[L] | (w[0] << r)
+//     v = L + 1 + j   (w[j] >> (64 - r)) | (w[j+1] << r)
+// and 0 .. L - 1 are the words themselves.  A lane's primary word is the one at its column
+// wrapped by whole words (v < 0: L; v >= nw: v - nw), the second word sits at seam_second_col.
+__host__ __device__ inline int seam_primary_col(int v, int L) { return v < 0 ? L : v > L ? v - L - 1 : v; }
+__host__ __device__ inline int seam_second_col(int v, int L) { return v < 0 ? L - 1 : v == L ? 0 : v - L; }
+// (lo >> s) | (hi << (32 - s)), s in 0 .. 32
+__host__ __device__ inline uint32_t seam_funnel32(uint32_t lo, uint32_t hi, int s)
+{
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> s);
+}
+// (lo >> a) | (hi << (64 - a)), a in 1 .. 63, of two words in the standard layout or (il) in the
+// interleaved one (even cells in the low dword, odd cells in the high one): there an even
+// a = 2 q funnels both dword pairs by q, and an odd a = 2 q + 1 swaps their roles -- the new
+// even dword is the odd dwords funnelled by q, the new odd dword the even ones by q + 1.
+// (odd = a & 1, passed apart: the kernel's lanes funnel by r or by 64 - r, amounts that differ
+// from lane to lane but have one parity, and that keeps this branch on the scalar unit)
+__host__ __device__ inline uint64_t seam_funnel(uint64_t lo, uint64_t hi, int a, bool odd, bool il)
+{
+    if (!il) return (lo >> a) | (hi << (64 - a));
+    const uint32_t le = (uint32_t)lo, lod = (uint32_t)(lo >> 32);
+    const uint32_t he = (uint32_t)hi, hod = (uint32_t)(hi >> 32);
+    const int q = a >> 1;
+    uint32_t e, o;
+    if (odd) {
+        e = seam_funnel32(lod, hod, q);
+        o = seam_funnel32(le, he, q + 1);
+    } else {
+        e = seam_funnel32(le, he, q);
+        o = seam_funnel32(lod, hod, q);
+    }
+    return ((uint64_t)o << 32) | e;
+}
+// virtual column v (-1 or >= L) from its primary word p and its second word s.  odd = r & 1:
+// r and 64 - r have one parity, so the interleaved funnel's form is the same for every lane
+// (the kernel passes it as a constant of its load stage's two forms).
+__host__ __device__ inline uint64_t seam_stitch(uint64_t p, uint64_t s, int v, int L, int r, bool odd,
+                                                bool il)
+{
+    const bool west = v < 0, last = v == L;
+    const uint64_t lo = west ? s : last ? 0ull : p, hi = west ? p : s;
+    return (last ? p : 0ull) | seam_funnel(lo, hi, west ? r : 64 - r, odd, il);
+}
+
+// width: the board's, for a launch across the row seam (width % 64 != 0: a seam code, tiles no
+// wider than the row); 0: a board of whole words
+bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg, int width = 0);
 int tile_waves(int turns, int tile_h, int tile_w, int seg);
 // resident workgroups per CU of that launch (occupancy API: VGPRs, LDS; 0 on error)
-int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg);
+int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg, int width = 0);
+// (gol_tile_seam.hip) the k_step_tile_seam instantiation of a code, or nullptr
+void *tile_seam_kernel(int code);
 // The tiles of one k_step_tile launch over `rows` rows of nw words.  A row's lane columns
 // make ntx = ceil(nl / tile_w) tile columns; when the last one is ragged (r < tile_w lanes)
 // and packs more row segments into a wave at its own width (G' = 64 / (r + 2) > G), it is cut

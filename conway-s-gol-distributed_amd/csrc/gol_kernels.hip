@@ -754,9 +754,16 @@ int auto_band_multi(int width, int rows, int lane_dwords)
     return (int)b;
 }
 
-bool multi_ok(int width, int turns, int variant)
+bool multi_ok(int width, int turns, int variant, int tile_code)
 {
-    return fast_path_ok(width) && turns >= 2 && turns <= multi_max_turns(variant);
+    if (turns < 2 || turns > multi_max_turns(variant)) return false;
+    if (variant != kMultiTile) return fast_path_ok(width);
+    // k_step_tile: any width of at least 256 cells.  Across the row seam (width % 64 != 0) only
+    // the codes with a seam instantiation; an odd word count has no two-word lanes.
+    if (width < 256) return false;
+    if (tile_code > 0 && width % 64 != 0 && !tile_code_seam(tile_code)) return false;
+    if (tile_code > 0 && ((width + 63) / 64) % 2 != 0 && tile_code >= 1000) return false;
+    return true;
 }
 
 bool multi_fits(int nw, int pitch, int rows)

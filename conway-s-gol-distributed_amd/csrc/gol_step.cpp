@@ -151,8 +151,8 @@ Launch plan_launch(gol_ctx *c, int64_t room)
         const int64_t nl = (room + s.tpl - 1) / s.tpl;
         const int k = (int)((room + nl - 1) / nl);
         const int band = band_for_depth(c, k);
-        if (!golk::multi_ok(c->cfg.width, k, s.multi_variant) ||
-            !golk::tile_shape_ok(c->nw, k, band, s.tile_w, s.tile_seg))
+        if (!golk::multi_ok(c->cfg.width, k, s.multi_variant, s.tile_seg) ||
+            !golk::tile_shape_ok(c->nw, k, band, s.tile_w, s.tile_seg, c->cfg.width))
             return L;
         return Launch{k, s.multi_variant, band, s.tile_w, s.tile_seg};
     }
@@ -164,7 +164,7 @@ Launch plan_launch(gol_ctx *c, int64_t room)
     }
     const int64_t nl = (room + s.tpl - 1) / s.tpl;
     const int k = (int)((room + nl - 1) / nl);
-    if (!golk::multi_ok(c->cfg.width, k, s.multi_variant)) return L;
+    if (!golk::multi_ok(c->cfg.width, k, s.multi_variant, s.tile_seg)) return L;
     return Launch{k, s.multi_variant, band_for_depth(c, k), s.tile_w, s.tile_seg};
 }
 
@@ -656,6 +656,28 @@ int gol_tile_count_codes(int32_t *codes, int32_t cap)
     if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
     for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileCountCodes[i];
     return n;
+}
+
+int gol_tile_seam_codes(int32_t *codes, int32_t cap)
+{
+    const int n = (int)std::size(golk::kTileSeamCodes);
+    if (cap < 0 || (cap > 0 && !codes)) return GOL_EINVAL;
+    for (int i = 0; i < std::min(n, (int)cap); ++i) codes[i] = golk::kTileSeamCodes[i];
+    return n;
+}
+
+int gol_seam_word(const uint64_t *row, int32_t width, int32_t v, int32_t layout, uint64_t *out)
+{
+    if (!row || !out || width < 256 || (layout != 0 && layout != 1)) return GOL_EINVAL;
+    const int nw = (width + 63) / 64, L = nw - 1, r = width % 64;
+    if (v < -1 || v > nw) return GOL_EINVAL;
+    const uint64_t p = row[golk::seam_primary_col(v, L)];
+    // whole words, or a column that is a real word: no stitch
+    *out = r == 0 || (v >= 0 && v < L)
+               ? p
+               : golk::seam_stitch(p, row[golk::seam_second_col(v, L)], v, L, r, (r & 1) != 0,
+                                 layout == 1);
+    return GOL_OK;
 }
 
 int gol_tile_persist_codes(int32_t *codes, int32_t cap)

@@ -220,7 +220,16 @@ struct RingArgs {
 // flags).  Only the waves holding a row of [K, K + TH) count: they never leave the trapezoid,
 // and one of them adds the waves' sums up after one barrier at the end of the launch -- one
 // global atomic per (workgroup, turn) with a non-zero count.
-template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false>
+// SEAM (k_step_tile_seam: a board whose width is no multiple of 64, r = width % 64 cells in the
+// row's last word L = nw - 1): the torus seam in x falls inside a word, so the lanes whose
+// virtual column is -1 or >= L (gol_kernels.h, seam_stitch) hold words stitched from two real
+// ones -- the wrapped cells sit where the padding bits were, and they are halo like any other.
+// Only the load stage (a second word per row for those lanes, in the tiles that touch the seam:
+// the first tile column and the ones that reach column L) and the store stage (the lane of
+// column L clears its bits r .. 63: the padding of both boards stays zero) differ; the turns
+// and the LDS exchange are the plain kernel's.  One word per lane, plain launches, no counts.
+template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false,
+          bool SEAM = false>
 __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                                           uint64_t *__restrict__ out, const StepArgs &a,
                                           int turns, const TilePos &pos,
@@ -269,6 +278,22 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         gx += gx < 0 ? nl : 0;
         gx -= gx >= nl ? nl : 0;
     }
+    static_assert(!SEAM || (W == 1 && !PERSIST && !RING && !CNT && ORD != 3 && ORD < 7),
+                  "seam launches: plain k_step_tile, one word per lane, no counts");
+    // SEAM: the lane's virtual column, and the byte distance from its primary word (column gx,
+    // wrapped by whole words) to its second one; seam_tile is wave-uniform
+    [[maybe_unused]] bool seam_tile = false, seam_lane = false;
+    [[maybe_unused]] int seam_v = 0;
+    [[maybe_unused]] uint32_t seam_d = 0;
+    if constexpr (SEAM) {
+        const int L = nl - 1;
+        seam_tile = x0 == 0 || x0 + TW >= L;
+        seam_v = x0 - 1 + (live ? col : 0);
+        seam_lane = seam_tile && live && (seam_v < 0 || seam_v >= L);
+        // (a column past nw is junk no stored cell's cone reaches: any word inside the row)
+        const int g2 = seam_lane ? min(seam_second_col(seam_v, L), L) : gx;
+        seam_d = (uint32_t)(g2 - gx) * 8u;
+    }
     const int M = a.modrows;
     const uint32_t pitch_b = (uint32_t)a.pitch * 8u;
     const uint32_t span = (uint32_t)M * pitch_b;
@@ -314,7 +339,9 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     // No segment of the wave wraps past the buffer's last row inside its SEG rows (one ballot;
     // nearly every wave): one lane offset, the rows stepped by the scalar offset of the buffer
     // instruction -- no VALU per row.  Otherwise the offset wraps row by row.
-    if (!kHalo && __builtin_amdgcn_ballot_w64(r + SEG > M) == 0) {
+    // (SEAM: the seam tiles load in their own way, below)
+    if (SEAM && seam_tile) {
+    } else if (!kHalo && __builtin_amdgcn_ballot_w64(r + SEG > M) == 0) {
 #pragma unroll
         for (int i = 0; i < SEG; ++i) load_row(i, off, (uint32_t)i * pitch_b);
     } else {
@@ -323,6 +350,67 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
             load_row(i, off, 0);
             off += lstep;
             off = off >= span ? off - span : off;        // (the column stays < pitch_b)
+        }
+    }
+    // SEAM: a seam tile loads two words per row -- the primary word and, for the seam lanes,
+    // the second one (the other lanes read their primary word twice) -- and stitches, kSeamChunk
+    // rows at a time: the loads of a chunk are in flight together, and no more than that many
+    // word pairs are held beside the segment (all SEG at once would be 2 SEG more registers).
+    // No lane branches: the lanes that are no seam lanes select their primary word.  Four forms
+    // of the stage, picked on the scalar unit: the parity of r (seam_funnel's two forms, each
+    // straight-line code) x the rows stepped by the instruction's scalar offset (no segment of
+    // the wave wraps past the buffer's last row) or by offsets that wrap row by row.
+    if constexpr (SEAM) {
+        if (seam_tile) {
+            const int L = nl - 1, rb = a.width & 63;
+            auto seam_load = [&](auto ODD, auto STEP) {
+                constexpr bool odd = decltype(ODD)::value, step = decltype(STEP)::value;
+                constexpr int kSeamChunk = 4;
+                uint32_t o1 = off_first, o2 = off_first + seam_d;
+#pragma unroll
+                for (int c0 = 0; c0 < SEG; c0 += kSeamChunk) {
+                    u32x2 p[kSeamChunk], t[kSeamChunk];
+#pragma unroll
+                    for (int j = 0; j < kSeamChunk; ++j) {
+                        if (c0 + j < SEG) {
+                            const uint32_t so = step ? (uint32_t)(c0 + j) * pitch_b : 0u;
+                            p[j] = __builtin_amdgcn_raw_buffer_load_b64(rin, o1, so, kLoadAux);
+                            t[j] = __builtin_amdgcn_raw_buffer_load_b64(rin, o2, so, kLoadAux);
+                            if constexpr (!step) {
+                                o1 += lstep;
+                                o1 = o1 >= span ? o1 - span : o1;
+                                o2 += lstep;             // (its column stays < pitch_b too)
+                                o2 = o2 >= span ? o2 - span : o2;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < kSeamChunk; ++j) {
+                        if (c0 + j < SEG) {
+                            const uint64_t pw = ((uint64_t)p[j].y << 32) | p[j].x;
+                            const uint64_t sw = ((uint64_t)t[j].y << 32) | t[j].x;
+                            const uint64_t w = seam_stitch(pw, sw, seam_v, L, rb, odd, true);
+                            v[c0 + j][0] = seam_lane ? (uint32_t)w : p[j].x;
+                            v[c0 + j][1] = seam_lane ? (uint32_t)(w >> 32) : p[j].y;
+                        }
+                    }
+                    // (the next chunk's loads wait for this chunk's words: their address passes
+                    // through an empty asm that reads the chunk's last stitched row)
+                    if (c0 + kSeamChunk < SEG)
+                        asm volatile("" : "+v"(o1), "+v"(o2) : "v"(v[c0 + kSeamChunk - 1][0]),
+                                     "v"(v[c0 + kSeamChunk - 1][1]));
+                }
+            };
+            using std::false_type;
+            using std::true_type;
+            const bool nowrap = __builtin_amdgcn_ballot_w64(r + SEG > M) == 0;
+            if (rb & 1) {
+                if (nowrap) seam_load(true_type{}, true_type{});
+                else seam_load(true_type{}, false_type{});
+            } else {
+                if (nowrap) seam_load(false_type{}, true_type{});
+                else seam_load(false_type{}, false_type{});
+            }
         }
     }
 
@@ -968,6 +1056,22 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         const int top = min(K + TH, a.row_hi - (y0 - K));    // (wave-uniform)
         const int lo = min(max(K - t0, 0), SEG), hi = min(max(top - t0, 0), SEG);
         uint32_t so = (uint32_t)(y0 - K + t0) * pitch_b + (uint32_t)(x0 + sc - 1) * (8u * W);
+        // SEAM: the tile that holds column L (wave-uniform) clears that lane's bits r .. 63 --
+        // the wrapped cells it carried through the turns -- so the padding stays zero
+        if constexpr (SEAM) {
+            const int L = nl - 1;
+            if (x0 <= L && x0 + TW > L) {
+                const int rb = a.width & 63;                 // (1 .. 63: a seam launch)
+                const bool lastc = x0 + sc - 1 == L;
+                const uint32_t me = lastc ? ~0u >> (32 - ((rb + 1) >> 1)) : ~0u;
+                const uint32_t mo = lastc ? (1u << (rb >> 1)) - 1u : ~0u;
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) {
+                    v[i][0] &= me;
+                    v[i][1] &= mo;
+                }
+            }
+        }
         // Every storing lane of the wave stores its whole segment (one ballot; every wave but
         // the tile's first and last, and the board's last tile row): all SEG rows under one
         // exec mask, stepped by the instruction's scalar offset.  The lane's offset is that of
@@ -1230,6 +1334,21 @@ __global__ __launch_bounds__(1024, (ORD == 7 ? 6 : 1)) void k_step_tile(const ui
     const int tile = tile_of_block(L.ntiles);
     if (tile >= L.ntiles) return;                        // the whole workgroup
     tile_pass<SEG, ORD, W, false>(in, out, a, turns, tile_pos(a, L, tile));
+}
+
+// k_step_tile across the row seam (tile_pass SEAM; the instantiations: golk::kTileSeamCodes,
+// gol_tile_seam.hip).  Its own entry point: the kernels of whole-word boards stay as they are.
+// (the waves per SIMD of the plain kernel of the same code are asked for: left to itself the
+// compiler takes 65 VGPRs at SEG 16 and 81 at SEG 24 for the load stage's sake, one register
+// past 8 and 6 waves; held to the bound it spills one 64-bit value once, before the first turn)
+template <int SEG, int ORD>
+__global__ __launch_bounds__(1024, (SEG <= 16 ? 8 : 6)) void k_step_tile_seam(const uint64_t *__restrict__ in,
+                                                            uint64_t *__restrict__ out, StepArgs a,
+                                                            int turns, TileLaunch L)
+{
+    const int tile = tile_of_block(L.ntiles);
+    if (tile >= L.ntiles) return;                        // the whole workgroup
+    tile_pass<SEG, ORD, 1, false, false, false, true>(in, out, a, turns, tile_pos(a, L, tile));
 }
 
 // k_step_tile with the per-turn alive counts fused (tile_pass CNT; the instantiations:

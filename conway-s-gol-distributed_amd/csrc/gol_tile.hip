@@ -7,6 +7,7 @@
 #include <iterator>
 #include <map>
 #include <mutex>
+#include <tuple>
 
 namespace golk {
 
@@ -218,9 +219,14 @@ void *tile_cnt_kernel(int code)
     }
 }
 
-bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg)
+bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg, int width)
 {
     if (turns < 2 || turns > 64 || tile_h < 1 || tile_w < 1 || tile_w + 2 > 64 || !tile_kernel(seg))
+        return false;
+    // across the row seam: a code with a seam instantiation, and a tile no wider than the row
+    // (its lane columns then stay within [-1, nw]: two real words per stitched column)
+    if (width > 0 && width % 64 != 0 &&
+        (!tile_code_seam(seg) || !tile_seam_kernel(seg) || tile_w > nw || width < 256))
         return false;
     if (!GOL_TOOLS && !tile_code_shipped(seg) && !(GOL_TILE_W2_SEG12 && seg % 1000 == 112) &&
         !(GOL_TILE_W2_SEG12 && seg % 1000 == 512) && !(GOL_TILE_PAIR && seg / 100 == 3))
@@ -244,23 +250,24 @@ int tile_waves(int turns, int tile_h, int tile_w, int seg)
     return (nseg + G - 1) / G;
 }
 
-int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg)
+int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg, int width)
 {
-    void *fn = tile_kernel(seg);
+    const bool seam = width > 0 && width % 64 != 0;      // (the seam kernel's own registers)
+    void *fn = seam ? tile_seam_kernel(seg) : tile_kernel(seg);
     if (!fn) return 0;
     const int waves = tile_waves(turns, tile_h, tile_w, seg);
     if (waves < 1 || waves > kTileMaxWaves) return 0;
     // (the planner asks for thousands of shapes: cache per (kernel, waves))
     static std::mutex mu;
-    static std::map<std::pair<int, int>, int> cache;
+    static std::map<std::tuple<int, int, bool>, int> cache;
     std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find({seg, waves});
+    auto it = cache.find({seg, waves, seam});
     if (it != cache.end()) return it->second;
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &blocks, fn, 64 * waves, tile_lds_bytes_code(64 * waves, seg)) != hipSuccess)
         blocks = 0;
-    cache[{seg, waves}] = blocks;
+    cache[{seg, waves, seam}] = blocks;
     return blocks;
 }
 
@@ -308,7 +315,7 @@ long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg, int turn
 hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
 {
     const int rows = a.row_hi - a.row_lo;
-    if (!tile_shape_ok(a.nw, turns, a.band, a.tile_w, a.tile_seg)) return hipErrorInvalidValue;
+    if (!tile_shape_ok(a.nw, turns, a.band, a.tile_w, a.tile_seg, a.width)) return hipErrorInvalidValue;
     // (ORD 3 with GOL_TILE_PAIR pairs tiles by index: tile_grid leaves its grid rectangular)
     const TileGrid g = tile_grid(a.nw, rows, turns, a.band, a.tile_w, a.tile_seg);
     const int ntx = g.ntx_main;
@@ -332,7 +339,11 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
     // a.counts: `turns` consecutive zeroed slots of kShards accumulators, one per turn of the
     // launch -- the counted kernel, and an error for a code without one (never the uncounted
     // kernel with the counts dropped)
-    void *fn = a.counts ? tile_cnt_kernel(a.tile_seg) : tile_kernel(a.tile_seg);
+    // a width that is no multiple of 64: the seam kernel (which has no counted form)
+    const bool seam = a.width % 64 != 0;
+    void *fn = seam ? (a.counts ? nullptr : tile_seam_kernel(a.tile_seg))
+               : a.counts ? tile_cnt_kernel(a.tile_seg)
+                          : tile_kernel(a.tile_seg);
     if (!fn || (a.counts && !tile_code_counted(a.tile_seg))) return hipErrorInvalidValue;
     StepArgs args = a;
     const uint64_t *in = a.in;

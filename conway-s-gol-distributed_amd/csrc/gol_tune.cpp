@@ -46,6 +46,27 @@ constexpr bool all_shipped(const int (&codes)[N])
     return true;
 }
 
+// A board whose width is no multiple of 64 runs k_step_tile across the row seam: the model's
+// ranking and the measured search draw their codes from this list alone there (seam_pickable),
+// and every one of them has a seam instantiation
+constexpr int kSeamSegs[] = {2, 16, 102, 104, 106, 108, 112, 116, 516, 524};
+template <size_t N>
+constexpr bool all_seam(const int (&codes)[N])
+{
+    for (int c : codes)
+        if (!golk::tile_code_seam(c)) return false;
+    return true;
+}
+static_assert(all_seam(kSeamSegs) && all_shipped(kSeamSegs),
+              "a tile code outside golk::kTileSeamCodes");
+bool seam_pickable(int width, int seg)
+{
+    if (width % 64 == 0) return true;
+    for (int c : kSeamSegs)
+        if (c == seg) return true;
+    return false;
+}
+
 }  // namespace
 
 // Modelled time per turn of k_step_tile at one shape, fitted to the
@@ -56,12 +77,12 @@ constexpr bool all_shipped(const int (&codes)[N])
 // and the LDS exchange -- cheaper to hide with >= 2 workgroups per CU (~80 % of the issue
 // rate and ~700 cycles a turn) than with one (~70 %, ~900).  Residency from the occupancy
 // API (the kernel's VGPRs and dynamic LDS).
-double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg)
+double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg, int width)
 {
-    if (!golk::tile_shape_ok(nw, K, th, tw, seg)) return 0;
+    if (!golk::tile_shape_ok(nw, K, th, tw, seg, width)) return 0;
     const long long tiles = golk::tile_count(nw, rows, th, tw, seg, K);   // (what is launched)
     const int waves = golk::tile_waves(K, th, tw, seg);
-    const int wgpc = golk::tile_blocks_per_cu(K, th, tw, seg);         // VGPRs, LDS
+    const int wgpc = golk::tile_blocks_per_cu(K, th, tw, seg, width);  // VGPRs, LDS
     if (wgpc <= 0) return 0;
     const long long slots = (long long)ncu * wgpc;
     const long long rounds = (tiles + slots - 1) / slots;
@@ -79,7 +100,7 @@ double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg)
 // the tallest tile the workgroup holds (16 waves) and the heights whose tile count fills 1..4
 // resident tiles per CU or a few more tile rows.
 // cnt: for a count engine's fused launches -- codes with a counted instantiation only.
-std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt)
+std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt, int width)
 {
     // SEG, and SEG + 100 for the interior-rows-first turn order (gol_tile.hip)
     static constexpr int kSegs[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 40, 48,
@@ -98,6 +119,7 @@ std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool
             const long long ntx = (nw + tw - 1) / tw;
             for (int seg : kSegs) {
                 if (cnt && !golk::tile_code_counted(seg)) continue;
+                if (!seam_pickable(width, seg)) continue;
                 const int thmax = golk::kTileMaxWavesHost * G * (seg % 100) - 2 * K;
                 if (thmax < 1) continue;
                 std::vector<long long> ntys;
@@ -107,7 +129,7 @@ std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool
                     ntys.push_back(std::max(nty0, ((long long)ncu * per_cu + ntx - 1) / ntx));
                 for (long long nty : ntys) {
                     const int th = (int)std::max<long long>(1, (rows + nty - 1) / nty);
-                    const double m = tile_model_us(ncu, nw, rows, K, th, tw, seg);
+                    const double m = tile_model_us(ncu, nw, rows, K, th, tw, seg, width);
                     if (m > 0 && (best.K == 0 || m < best.model_us)) best = {K, th, tw, seg, m};
                 }
             }
@@ -160,7 +182,9 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
 {
     *us = 0.f;
     const int nw = c->nw, rows = c->buf_rows;
-    if (nw % W) return TileShape{};
+    const int width = c->cfg.width;
+    const bool seam = width % 64 != 0;               // (one word per lane, the seam codes)
+    if (nw % W || (seam && W != 1)) return TileShape{};
     // a count engine searches the codes with a counted instantiation (one word per lane) and
     // times the counted kernel: the counts of each launch's turns go to the ring's first slots
     // (the ring is cleared when the create ends)
@@ -194,6 +218,7 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
         segs.erase(std::remove_if(segs.begin(), segs.end(),
                                   [](int sg) { return !golk::tile_code_counted(sg); }),
                    segs.end());
+    if (seam) segs.assign(std::begin(kSeamSegs), std::end(kSeamSegs));
     struct P { int K, wv, tw, seg, th = 0; };          // th > 0: this height (<= wv's)
     auto shape = [&](const P &p) -> TileShape {
         const int G = 64 / (p.tw + 2);
@@ -201,7 +226,7 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
         if (p.th > 0) th = std::min(th, p.th);
         th = std::min(th, rows);
         if (th < std::min(8, rows) || (cnt && !golk::tile_code_counted(p.seg)) ||
-            !golk::tile_shape_ok(nw, p.K, th, p.tw, p.seg))
+            !seam_pickable(width, p.seg) || !golk::tile_shape_ok(nw, p.K, th, p.tw, p.seg, width))
             return TileShape{};
         return TileShape{p.K, th, p.tw, p.seg, 0};
     };
@@ -252,7 +277,8 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
         TileShape t0 = shape(cur);
         if (!t0.K) {                          // (tiny boards: shallower SEG)
             for (int sg : {8, 4, 2}) {
-                cur.seg = sg + 1000 * (W - 1);
+                // (across the seam: the short seam codes 108, 104, 106)
+                cur.seg = seam ? (sg == 2 ? 106 : 100 + sg) : sg + 1000 * (W - 1);
                 if ((t0 = shape(cur)).K) break;
             }
         }
@@ -344,7 +370,7 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
                 for (long long nty = (rows + t0.th - 1) / t0.th; nty <= 4ll * rows; ++nty) {
                     const int th = (int)((rows + nty - 1) / nty);
                     if (th < 8) break;
-                    const int wg = golk::tile_blocks_per_cu(base.K, th, base.tw, base.seg);
+                    const int wg = golk::tile_blocks_per_cu(base.K, th, base.tw, base.seg, width);
                     if (wg <= 0) continue;
                     if (ntx * nty <= (long long)r * c->ncu * wg) {
                         if (th != t0.th) improve(P{base.K, base.wv, base.tw, base.seg, th});
@@ -412,7 +438,8 @@ void autotune_small(gol_ctx *c)
     if (!t1.K && !t2.K) return;
     apply_tile(c, two ? t2 : t1);
     c->shape.tuned_us_per_turn = two ? us2 : us1;
-    if (!(c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN)) blocks_tune_persist(c);   // (K1p has no counted form)
+    // (K1p has no counted form, and none for the widths k_step_tile alone blocks)
+    if (!(c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) && !c->tile_only) blocks_tune_persist(c);
 }
 
 // ---------------------------------------------------------------- autotune_multi

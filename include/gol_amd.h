@@ -75,7 +75,9 @@ typedef struct gol_ctx gol_ctx;
                                             k_step_tile: an engine whose multi-turn kernel is
                                             k_step_tile at a gol_tile_count_codes code keeps its
                                             temporal blocking, every other one runs one turn per
-                                            launch */
+                                            launch -- among them every engine whose width is no
+                                            multiple of 128 (k_step_tile has no counted form
+                                            across the row seam) */
 #define GOL_FLAG_FORCE_GENERIC     0x2u  /* use the generic stencil even when the fast one applies */
 #define GOL_FLAG_NO_AUTOTUNE       0x4u  /* skip the create-time (turns per launch, band) timing
                                             sweep on large boards (results never depend on it) */
@@ -90,7 +92,11 @@ typedef struct gol_config {
     uint32_t flags;       /* GOL_FLAG_*                                                   */
     int32_t  band_rows;   /* rows per wavefront band in the stencil; 0 = auto             */
     int32_t  turns_per_launch; /* temporal blocking: turns fused per stencil pass (1 = off;
-                                  0 = default); results are identical for every value   */
+                                  0 = default); results are identical for every value.
+                                  Widths of at least 256 cells block: multiples of 128 on
+                                  every multi-turn kernel, the others on k_step_tile alone
+                                  (gol_tile_seam_codes where width % 64 != 0); narrower
+                                  boards run one turn per launch                        */
 } gol_config;
 
 typedef struct gol_info {
@@ -101,7 +107,9 @@ typedef struct gol_info {
     int32_t  fast_path;         /* 1 = the LDS-free DPP stencil (width % 128 == 0, >= 256) */
     int32_t  band_rows;         /* effective band height                              */
     int32_t  halo_valid;        /* strip mode: turns left before the next exchange    */
-    int32_t  turns_per_launch;  /* effective temporal-blocking depth                   */
+    int32_t  turns_per_launch;  /* effective temporal-blocking depth (1: widths below 256,
+                                   forced-generic engines, count engines of a width that
+                                   is no multiple of 128, blocking_limited)             */
     int32_t  device;
     int64_t  turn;              /* completed turns since load                          */
     int64_t  nonbinary_cells;   /* cells that were neither 0 nor 255 at load           */
@@ -200,6 +208,18 @@ int gol_tile_grid(int32_t nw, int32_t rows, int32_t turns, int32_t tile_h, int32
 /* The subset with a counted form (k_step_tile with the per-turn alive counts fused): the codes
  * a GOL_FLAG_COUNT_EVERY_TURN engine runs multi-turn launches on; same convention. */
 int gol_tile_count_codes(int32_t *codes, int32_t cap);
+/* The subset with a form for boards whose width is no multiple of 64 (k_step_tile across the
+ * row seam: the torus wraps in x inside the row's last word): the codes such an engine runs
+ * multi-turn launches on; same convention. */
+int gol_tile_seam_codes(int32_t *codes, int32_t cap);
+/* The word a k_step_tile lane holds at virtual lane column v of a row of `width` cells: cells
+ * 64 v .. 64 v + 63 (mod width), bit b = cell 64 v + b.  row: the row's ceil(width / 64) words
+ * (padding bits zero) in `layout` (0 standard, 1 interleaved: even cells in the low dword, odd
+ * cells in the high one); *out is in the same layout.  v in [-1, words per row]: the columns a
+ * tile no wider than the row loads.  This is the host build of the kernel's own stitch.
+ * GOL_EINVAL for a v outside that range, width < 256, an unknown layout or null pointers.
+ * Needs no device. */
+int gol_seam_word(const uint64_t *row, int32_t width, int32_t v, int32_t layout, uint64_t *out);
 /* The subset of those the persistent tile kernel (K1p: small torus boards, tiles resident
  * across blocks of turns) runs; same convention. */
 int gol_tile_persist_codes(int32_t *codes, int32_t cap);
