@@ -63,6 +63,7 @@ struct Launch {
 constexpr int kPlanMax = 128;               // launch plans cover gol_step / halo windows up to this
 constexpr int kSeqMax = 32;                 // gol_step calls this short run a timed sequence
 constexpr size_t kLastCap = 4096;           // gol_last_launches records at most this many
+constexpr int kMaxStepChunks = 64;          // row chunks of one launch at the most (GOL_STEP_CHUNKS)
 
 // a read-only call (gol_snapshot, gol_read_*, ...) run by a stepping thread at a launch boundary
 struct Job {
@@ -163,6 +164,10 @@ struct gol_ctx {
     hipStream_t stream = nullptr;
     hipStream_t side = nullptr;              // boundary-band launches of gol_step_overlap
     hipEvent_t ev_side = nullptr, ev_main = nullptr;
+    // the chunked pipeline of gol_step (gol_step.cpp, launch_chunked): one event per chunk and
+    // launch parity, created at first use; the chunk kernels of the last gol_step
+    hipEvent_t chunk_ev[2][kMaxStepChunks] = {};
+    long long last_chunks = 0;
     long long turn = 0;
     long long launches = 0;
     int halo_valid = 0;
@@ -310,6 +315,16 @@ Launch plan_launch(gol_ctx *c, int64_t room);
 bool stepping_il(const gol_ctx *c, int k);
 int ensure_layout(gol_ctx *c, bool il);
 hipError_t pg_prepare(gol_ctx *c, golk::StepArgs &a, int k);
+// Row chunks of one k_step_tile launch over `rows` buffer rows on tiles of tile_h rows: the
+// n + 1 bounds of n <= want chunks, cut on multiples of tile_h (the tile rows spread evenly:
+// floor(tile rows / n) each, one more for the last tile rows % n chunks; the ragged tile row
+// stays in the last chunk), every chunk at least min_rows tall -- fewer chunks when
+// `want` cannot have that; one chunk = {0, rows}.
+std::vector<int> chunk_bounds(int rows, int tile_h, int want, int min_rows);
+// deps[q]: the chunks of the previous launch (bounds pb, depth kp) that chunk q of the next
+// one (bounds nb, depth kn) must follow on the torus of `rows` buffer rows
+std::vector<std::vector<int>> chunk_deps(int rows, const std::vector<int> &pb, int kp,
+                                         const std::vector<int> &nb, int kn);
 
 // ---------------------------------------------------------------- gol_io.cpp
 void release_blocked(gol_ctx *c);

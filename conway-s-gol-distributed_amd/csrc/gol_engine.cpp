@@ -599,6 +599,9 @@ void gol_destroy(gol_ctx *c)
         if (c->side) (void)hipStreamDestroy(c->side);
         if (c->ev_side) (void)hipEventDestroy(c->ev_side);
         if (c->ev_main) (void)hipEventDestroy(c->ev_main);
+        for (auto &set : c->chunk_ev)
+            for (hipEvent_t e : set)
+                if (e) (void)hipEventDestroy(e);
         if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
         if (c->h_err) (void)hipHostFree(c->h_err);
     }

@@ -89,6 +89,62 @@ bool stepping_il(const gol_ctx *c, int k)
     return k > 1 && golk::multi_is_il(c->multi_words, c->shape.multi_variant);
 }
 
+std::vector<int> chunk_bounds(int rows, int tile_h, int want, int min_rows)
+{
+    if (rows < 1 || tile_h < 1) return {0, std::max(rows, 0)};
+    const int nty = (rows + tile_h - 1) / tile_h;
+    for (int n = std::min({want, nty, kMaxStepChunks}); n >= 2; --n) {
+        // floor(nty / n) tile rows each, one more for the last nty % n chunks; the last chunk
+        // holds the ragged tile row
+        const int base = nty / n, extra = nty % n;
+        std::vector<int> b(n + 1);
+        b[0] = 0;
+        for (int i = 0; i < n; ++i)
+            b[i + 1] = b[i] + (base + (i >= n - extra ? 1 : 0)) * tile_h;
+        b[n] = rows;
+        bool ok = true;
+        for (int i = 0; i < n; ++i) ok = ok && b[i + 1] - b[i] >= min_rows;
+        if (ok) return b;
+    }
+    return {0, rows};
+}
+
+namespace {
+// rows [a0, a1) of the torus (0 <= a0 < a1 <= rows) meet rows [b0, b1) taken modulo `rows`
+// (b0 may be negative and b1 past the end: a range widened by a launch's depth)
+bool rows_meet(int rows, int a0, int a1, long long b0, long long b1)
+{
+    if (b1 - b0 >= rows) return true;
+    for (long long s = -rows; s <= rows; s += rows)
+        if (a0 < b1 + s && b0 + s < a1) return true;
+    return false;
+}
+}  // namespace
+
+// Launch n reads board A and writes board B, launch n + 1 reads B and writes A.  Chunk q of
+// launch n + 1 computes its output rows from those rows of B widened by kn on both sides, and
+// chunk p of launch n computed its own from A widened by kp.  So q follows p when
+//   * p's output rows meet q's output rows widened by kn (q reads what p wrote), or
+//   * p's output rows widened by kp meet q's output rows (q overwrites what p read).
+// Nothing else needs an edge.  Two launches apart, chunk r of launch n + 2 overwrites rows of B
+// that chunks p of launch n wrote: take a row x of both.  The chunk q of launch n + 1 that
+// holds x among its output rows follows p by the first rule (x is in q's widened rows and in
+// p's output) and r follows q by the second (x is in q's widened rows and in r's output), so
+// the write-after-write order follows from the two edges.  Launch n + 2 reads A, which launch
+// n only read.
+std::vector<std::vector<int>> chunk_deps(int rows, const std::vector<int> &pb, int kp,
+                                         const std::vector<int> &nb, int kn)
+{
+    const int np = (int)pb.size() - 1, nn = (int)nb.size() - 1;
+    std::vector<std::vector<int>> deps(std::max(nn, 0));
+    for (int q = 0; q < nn; ++q)
+        for (int p = 0; p < np; ++p)
+            if (rows_meet(rows, pb[p], pb[p + 1], (long long)nb[q] - kn, (long long)nb[q + 1] + kn) ||
+                rows_meet(rows, nb[q], nb[q + 1], (long long)pb[p] - kp, (long long)pb[p + 1] + kp))
+                deps[q].push_back(p);
+    return deps;
+}
+
 }  // namespace goleng
 
 namespace {
@@ -468,26 +524,158 @@ int launch_one(gol_ctx *c, golk::StepArgs a, bool cnt, bool split, int in_lo, in
     return GOL_OK;
 }
 
+// ---------------------------------------------------------------- the chunked pipeline
+// Consecutive k_step_tile launches of a long torus step, each cut into row chunks on tile-row
+// boundaries (chunk_bounds) that alternate between the engine stream and c->side.  A chunk
+// follows only the chunks of the launch before that chunk_deps names -- stream order where they
+// ran on its own stream, else the latest of them on the other stream through its event -- so
+// the tail, the store burst and the load burst of one chunk run under another chunk's turns
+// (DESIGN.md "Launches overlapped in row chunks").  Events are waited on only after they were
+// recorded, the device waits on nothing else, and the kernels are the plain launch's.
+//
+// Chunks per launch in automatic mode: launches of at least kChunkMinRounds rounds of the
+// resident workgroups (CUs x tile_blocks_per_cu) get chunks of about kChunkRounds rounds.
+// 65536^2 (9.7 rounds per K = 30 launch), 960 turns, median of 3 alternating passes on one
+// box, k GCUPS by chunks per launch: 1: 131.8, 3: 125.9 (every chunk follows every chunk),
+// 4: 138.7, 5: 139.5, 6: 137.9, 7: 137.4, 8: 136.5, 10: 136.8, 20: 125.7
+// (profiles/chunk_overlap_ab.log) -- 5 chunks of 1.9 rounds.  A third stream was level at
+// best (5: 138.7, 8: 137.9, 10: 137.8) and is not built.
+constexpr int kChunkMinRounds = 4;
+constexpr double kChunkRounds = 2.0;
+
+struct ChunkPipe {
+    bool live = false;           // c->side holds chunks the engine stream has not joined
+    int parity = 0;              // the event set of the last chunked launch
+    int k = 0;                   // its depth
+    std::vector<int> bounds;     // its chunks' rows
+    std::vector<int> pos;        // chunk -> place in the issue order
+    std::vector<int> on_side;    // chunk -> ran on c->side
+    long long issued = 0;        // chunks issued since the pipe went live (stream alternation)
+};
+
+// GOL_STEP_CHUNKS, read per gol_step: 1 = off, n >= 2 = n chunks, unset / 0 = automatic (-1)
+int chunk_request()
+{
+    const char *env = getenv("GOL_STEP_CHUNKS");
+    const int n = env ? atoi(env) : 0;
+    return n <= 0 ? -1 : std::min(n, kMaxStepChunks);
+}
+
+// a launch the pipeline may cut (request: chunk_request's, once per step)
+bool chunk_eligible(const gol_ctx *c, const Launch &L, int request, bool cnt, bool ctl,
+                    hipStream_t xstream)
+{
+    return request != 1 && L.k > 1 && L.var == golk::kMultiTile && !is_strip(c) && !cnt &&
+           !c->blocked_pending && !xstream && !ctl && c->side &&
+           !c->readers.load(std::memory_order_relaxed);
+}
+
+int chunks_wanted(const gol_ctx *c, const Launch &L, int request)
+{
+    if (request > 0) return request;
+    const long long wg =
+        golk::tile_grid(c->nw, c->buf_rows, L.k, L.band, L.tw, L.seg).tiles();
+    const long long slots =
+        (long long)c->ncu * golk::tile_blocks_per_cu(L.k, L.band, L.tw, L.seg, c->cfg.width);
+    if (slots <= 0 || wg < kChunkMinRounds * slots) return 1;
+    return (int)std::min<long long>(kMaxStepChunks,
+                                    std::max(2ll, (long long)((double)wg / (kChunkRounds * (double)slots) + 0.5)));
+}
+
+hipEvent_t chunk_event(gol_ctx *c, int parity, int i)
+{
+    hipEvent_t &e = c->chunk_ev[parity][i];
+    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
+    return e;
+}
+
+// the engine stream joins the side stream: it waits for the side chunks of the last launch
+// (stream order covers every earlier one)
+int pipe_join(gol_ctx *c, ChunkPipe &p)
+{
+    if (!p.live) return GOL_OK;
+    for (size_t q = 0; q < p.on_side.size(); ++q)
+        if (p.on_side[q])
+            HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, c->chunk_ev[p.parity][q], 0));
+    p.live = false;
+    return GOL_OK;
+}
+
+// One launch of plan.k turns as the chunks `bounds` (>= 2).  a: the whole-buffer arguments with
+// the boards set.
+int launch_chunked(gol_ctx *c, ChunkPipe &p, golk::StepArgs a, const Launch &plan,
+                   const std::vector<int> &bounds)
+{
+    const int n = (int)bounds.size() - 1;
+    a.blocked = nullptr;
+    a.counts = nullptr;
+    a.band = plan.band;
+    a.multi_variant = plan.var;
+    a.tile_w = plan.tw;
+    a.tile_seg = plan.seg;
+    std::vector<std::vector<int>> deps(n);
+    std::vector<int> order(n), ready(n, -1);
+    for (int q = 0; q < n; ++q) order[q] = q;
+    if (p.live) {
+        deps = chunk_deps(c->buf_rows, p.bounds, p.k, bounds, plan.k);
+        // first the chunks whose last dependency was issued first
+        for (int q = 0; q < n; ++q)
+            for (int d : deps[q]) ready[q] = std::max(ready[q], p.pos[d]);
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int x, int y) { return ready[x] < ready[y]; });
+    } else {
+        // the side stream starts behind everything queued on the engine stream
+        HIP_OR_FAIL(c, hipEventRecord(c->ev_main, c->stream));
+        HIP_OR_FAIL(c, hipStreamWaitEvent(c->side, c->ev_main, 0));
+        p.issued = 0;
+    }
+    const int par = p.live ? p.parity ^ 1 : 0;
+    std::vector<int> pos(n), on_side(n);
+    for (int i = 0; i < n; ++i) {
+        const int q = order[i];
+        const int side = (int)(p.issued++ & 1);
+        hipStream_t s = side ? c->side : c->stream;
+        // the latest dependency on the other stream (same stream: stream order)
+        int far = -1;
+        for (int d : deps[q])
+            if (p.on_side[d] != side && (far < 0 || p.pos[d] > p.pos[far])) far = d;
+        if (far >= 0) HIP_OR_FAIL(c, hipStreamWaitEvent(s, c->chunk_ev[p.parity][far], 0));
+        golk::StepArgs b = a;
+        b.row_lo = bounds[q];
+        b.row_hi = bounds[q + 1];
+        HIP_OR_FAIL(c, golk::launch_step_multi(b, plan.k, s));
+        hipEvent_t e = chunk_event(c, par, q);
+        if (!e) return fail(c, GOL_EHIP, "hipEventCreate failed for a chunk event");
+        HIP_OR_FAIL(c, hipEventRecord(e, s));
+        pos[q] = i;
+        on_side[q] = side;
+    }
+    p.live = true;
+    p.parity = par;
+    p.k = plan.k;
+    p.bounds = bounds;
+    p.pos = std::move(pos);
+    p.on_side = std::move(on_side);
+    c->last_chunks += n;
+    return GOL_OK;
+}
+
 // gol_step / gol_step_overlap.  xstream != null: the first launch is split -- the rows
 // whose k-turn dependency cone stays inside the owned rows run on the engine stream at
 // once, the rows next to the halos run on the side stream after everything queued on
 // xstream (the caller's halo receives) -- and the engine stream joins the side stream
-// before the next launch.  (C linkage: the library exports this name.)
-extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
-              std::unique_lock<std::recursive_mutex> &lk)
+// before the next launch.  `pipe`: the chunked pipeline's state; the caller joins it.
+int step_loop(gol_ctx *c, int64_t turns, hipStream_t xstream,
+              std::unique_lock<std::recursive_mutex> &lk, ChunkPipe &pipe)
 {
-    if (is_strip(c) && turns > c->halo_valid)
-        return fail(c, GOL_ESTATE, "strip engine: %lld turns requested, halos valid for %d",
-                    (long long)turns, c->halo_valid);
-    DeviceGuard g(c->device);
     const bool cnt = (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) != 0;
     golk::StepArgs a = whole_buffer_args(c);
     a.band = c->band;
     a.multi_variant = c->shape.multi_variant;
     a.tile_w = c->shape.tile_w;
     a.tile_seg = c->shape.tile_seg;
-    Stepping stepping(c);
     EventRing ring;
+    const int chunk_req = chunk_request();
     const bool ctl = c->control_used.load();
     // a reader served during an earlier step does not shorten this one's queue: the bound
     // comes back when a reader is served during this step (a ticker's snapshot)
@@ -503,14 +691,44 @@ extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
     long long zero_hi = c->turn;             // count engines: see zero_count_slots
     c->last.clear();
     c->last_n = 0;
+    c->last_chunks = 0;
     for (int64_t t = 0; t < turns;) {
-        if (c->jobs_pending.load(std::memory_order_relaxed)) serve_jobs(c);
-        if (ctl)
+        if (c->jobs_pending.load(std::memory_order_relaxed)) {
+            if (int rc = pipe_join(c, pipe)) return rc;      // readers use the engine stream
+            serve_jobs(c);
+        }
+        if (ctl)                                 // (a controlled engine never chunks)
             if (int rc = obey_control(c, lk, &zero_hi)) return rc;
         int64_t room = turns - t;
         if (is_strip(c)) room = std::min<int64_t>(room, c->halo_valid);
         const Launch plan = fixed && fi < fixed->size() ? (*fixed)[fi++] : plan_launch(c, room);
         const int k = plan.k;
+        // The chunked pipeline: a launch is cut when the one before it was, or when the next
+        // one can be (a lone launch stays one kernel).  Its chunks are fixed here, at least as
+        // tall as its own and both neighbours' depths.
+        std::vector<int> chunks;
+        const int want = chunk_eligible(c, plan, chunk_req, cnt, ctl, xstream)
+                             ? chunks_wanted(c, plan, chunk_req)
+                             : 1;
+        if (want > 1) {                          // (a board too small for chunks plans nothing more)
+            // (the next launch as planned from here, before this one has advanced the engine: a
+            // prediction that only decides whether to start a pipeline and how tall the chunks
+            // are -- chunk_deps is right for any bounds, so a wrong guess costs overlap alone)
+            int k_next = 0;
+            if (turns - t - k >= 2) {
+                const Launch nx = fixed && fi < fixed->size() ? (*fixed)[fi]
+                                                              : plan_launch(c, turns - t - k);
+                if (chunk_eligible(c, nx, chunk_req, cnt, ctl, xstream) &&
+                    chunks_wanted(c, nx, chunk_req) > 1)
+                    k_next = nx.k;
+            }
+            if (pipe.live || k_next)
+                chunks = chunk_bounds(c->buf_rows, plan.band, want,
+                                      std::max({k, k_next, pipe.live ? pipe.k : 0}));
+        }
+        const bool chunked = chunks.size() > 2;
+        if (!chunked)                            // a whole launch, a conversion: join first
+            if (int rc = pipe_join(c, pipe)) return rc;
         // rows computed: torus -> all; strip -> [s, buf_rows - s) after turn s since exchange
         const int s0 = is_strip(c) ? c->cfg.halo - c->halo_valid : 0;
         if (is_strip(c)) {
@@ -548,8 +766,9 @@ extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
         }
         if (cnt)
             if (int rc = zero_count_slots(c, k, turns - t, &zero_hi)) return rc;
-        if (int rc = k > 1 ? launch_multi(c, a, plan, cnt, split, in_lo, in_hi)
-                           : launch_one(c, a, cnt, split, in_lo, in_hi))
+        if (int rc = chunked ? launch_chunked(c, pipe, a, plan, chunks)
+                     : k > 1 ? launch_multi(c, a, plan, cnt, split, in_lo, in_hi)
+                             : launch_one(c, a, cnt, split, in_lo, in_hi))
             return rc;
         if (split) {   // join: the next launch overwrites rows the side launches read
             HIP_OR_FAIL(c, hipEventRecord(c->ev_side, c->side));
@@ -573,14 +792,36 @@ extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
             c->blocked_pending = false;
             c->raw_turn0.clear();
         }
-        if (ctl || c->readers.load(std::memory_order_relaxed))
+        if (ctl || c->readers.load(std::memory_order_relaxed)) {
+            if (int rc = pipe_join(c, pipe)) return rc;      // (the ring marks the engine stream)
             if (int rc = bound_queue(c, ring)) return rc;
+        }
     }
+    if (int rc = pipe_join(c, pipe)) return rc;
     if (c->blocked && !c->blocked_pending) {
         HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
         release_blocked(c);
     }
     return GOL_OK;
+}
+
+// (C linkage: the library exports this name.)
+extern "C" int step_impl(gol_ctx *c, int64_t turns, hipStream_t xstream,
+              std::unique_lock<std::recursive_mutex> &lk)
+{
+    if (is_strip(c) && turns > c->halo_valid)
+        return fail(c, GOL_ESTATE, "strip engine: %lld turns requested, halos valid for %d",
+                    (long long)turns, c->halo_valid);
+    DeviceGuard g(c->device);
+    Stepping stepping(c);                        // (its destructor serves readers: after the join)
+    ChunkPipe pipe;
+    const int rc = step_loop(c, turns, xstream, lk, pipe);
+    if (rc < 0 && pipe.issued > 0) {
+        // an error after chunks went out on both streams: drain them before the caller sees it
+        (void)hipStreamSynchronize(c->side);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -626,6 +867,35 @@ int gol_last_launch_tiles(gol_ctx *c, int32_t *tile_w, int32_t *tile_seg, int32_
         block_turns[i] = t ? depth : 0;
     }
     return (int)std::min<long long>(c->last_n, 0x7fffffff);
+}
+
+int gol_last_step_chunks(gol_ctx *c)
+{
+    if (!c) return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    return (int)std::min<long long>(c->last_chunks, 0x7fffffff);
+}
+
+int gol_step_chunk_plan(int32_t rows, int32_t k_prev, int32_t tile_h_prev, int32_t chunks_prev,
+                        int32_t k_next, int32_t tile_h_next, int32_t chunks_next, int32_t *counts,
+                        int32_t *prev_bounds, int32_t *next_bounds, uint8_t *deps, int32_t cap)
+{
+    if (rows < 1 || k_prev < 1 || k_next < 1 || tile_h_prev < 1 || tile_h_next < 1 ||
+        chunks_prev < 1 || chunks_next < 1 || cap < 1 || chunks_prev > cap || chunks_next > cap ||
+        !counts || !prev_bounds || !next_bounds || !deps)
+        return GOL_EINVAL;
+    const int min_rows = std::max(k_prev, k_next);
+    const std::vector<int> pb = chunk_bounds(rows, tile_h_prev, chunks_prev, min_rows);
+    const std::vector<int> nb = chunk_bounds(rows, tile_h_next, chunks_next, min_rows);
+    const auto d = chunk_deps(rows, pb, k_prev, nb, k_next);
+    counts[0] = (int32_t)pb.size() - 1;
+    counts[1] = (int32_t)nb.size() - 1;
+    std::copy(pb.begin(), pb.end(), prev_bounds);
+    std::copy(nb.begin(), nb.end(), next_bounds);
+    std::fill(deps, deps + (size_t)cap * cap, (uint8_t)0);
+    for (size_t q = 0; q < d.size(); ++q)
+        for (int p : d[q]) deps[q * cap + p] = 1;
+    return GOL_OK;
 }
 
 int gol_tile_codes(int32_t *codes, int32_t cap)

@@ -124,6 +124,10 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(ctypes.c_int32),
                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "gol_last_step_chunks": (_i32, [_vp]),
+    "gol_step_chunk_plan": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_int32), _u8p, _i32]),
     "gol_tile_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_grid": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int32)]),
     "gol_tile_count_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),

@@ -138,6 +138,10 @@ class Engine:
         k = 4 if blocks else 3
         return [tuple(arrs[j][i] for j in range(k)) for i in range(min(n, cap))]
 
+    def last_step_chunks(self) -> int:
+        """Chunk kernels the last step() ran (0: every launch was one kernel)."""
+        return self._c(self._L.gol_last_step_chunks(self._h))
+
     # -- overlapped halo exchange (gol_stream_wait / gol_step_overlap)
     def stream_wait(self, stream_ptr: int):
         """Make `stream_ptr` wait for the work queued on the engine so far."""

@@ -193,6 +193,22 @@ int gol_last_launches(gol_ctx *ctx, int32_t *turns, int32_t *kernel, int32_t *ba
  * gol_last_launches. */
 int gol_last_launch_tiles(gol_ctx *ctx, int32_t *tile_w, int32_t *tile_seg, int32_t *waves,
                           int32_t *block_turns, int32_t cap);
+/* The chunk kernels the last gol_step ran: a long torus step cuts consecutive k_step_tile
+ * launches into row chunks on two streams so that one chunk's tail, stores and loads run under
+ * another's turns (GOL_STEP_CHUNKS in the environment, read per gol_step: 1 = off, n >= 2 = n
+ * chunks per launch, unset or 0 = automatic).  0: every launch ran as one kernel.
+ * gol_last_launches still reports one entry per launch.  Or a negative GOL_E* code. */
+int gol_last_step_chunks(gol_ctx *ctx);
+/* The chunk plan of two consecutive launches over `rows` buffer rows of a torus: the previous
+ * one of k_prev turns on tiles of tile_h_prev rows asked for chunks_prev chunks, the next one
+ * likewise.  counts[0..1]: the chunks each gets (cut on multiples of its tile height, every
+ * chunk at least max(k_prev, k_next) rows tall: fewer than asked when they would not be);
+ * prev_bounds / next_bounds: counts[i] + 1 row bounds; deps[q * cap + p] = 1 when chunk q of
+ * the next launch must follow chunk p of the previous one.  cap >= both requests: the arrays
+ * hold cap + 1 bounds and cap x cap bytes.  Needs no device. */
+int gol_step_chunk_plan(int32_t rows, int32_t k_prev, int32_t tile_h_prev, int32_t chunks_prev,
+                        int32_t k_next, int32_t tile_h_next, int32_t chunks_next, int32_t *counts,
+                        int32_t *prev_bounds, int32_t *next_bounds, uint8_t *deps, int32_t cap);
 /* The k_step_tile segment codes this library runs (planner introspection for the parity
  * tests: every code the shape search can pick has an oracle test).  Writes min(n, cap) codes,
  * returns n.  Needs no device. */
