@@ -48,15 +48,15 @@ def _fit(h, want, k=K, th=TH):
 _RUNS = {}
 
 
-def _boards(oracle, h, turns_list):
+def _boards(oracle, h, turns_list, w=W):
     """(start, boards after each cumulative turn count): computed once per key and shared;
     callers do not modify them."""
-    key = (h, tuple(turns_list))
+    key = (w, h, tuple(turns_list))
     if key not in _RUNS:
-        start = oracle.gen_random(900 + h, W, h)
+        start = oracle.gen_random(900 + h + (w if w != W else 0), w, h)
         boards, cur = [], start
         for t in turns_list:
-            cur = oracle.bit_run(cur, W, t)
+            cur = oracle.bit_run(cur, w, t)
             boards.append(cur)
         for a in [start] + boards:
             a.setflags(write=False)
@@ -64,8 +64,8 @@ def _boards(oracle, h, turns_list):
     return _RUNS[key]
 
 
-def _engine(gol, h, k=K, th=TH, **kw):
-    return gol.Engine(W, h, device=0, band_rows=th, turns_per_launch=k, **kw)
+def _engine(gol, h, k=K, th=TH, w=W, **kw):
+    return gol.Engine(w, h, device=0, band_rows=th, turns_per_launch=k, **kw)
 
 
 def _expect(n):
@@ -179,7 +179,7 @@ def test_one_turn_step_after_chunks(gol, oracle, monkeypatch, code):
     whole board on the engine stream, after every side chunk (joined when the first step
     returned)."""
     h = 203
-    start, (_, want) = _boards(oracle, h, (TURNS, 1))
+    start, (prev, want) = _boards(oracle, h, (TURNS, 1))
     _pin(monkeypatch, code, 4)
     with _engine(gol, h) as e:
         e.load_packed(start)
@@ -188,8 +188,94 @@ def test_one_turn_step_after_chunks(gol, oracle, monkeypatch, code):
         e.step(1)
         assert [k for k, _, _ in e.last_launches()] == [1]
         assert e.last_step_chunks() == 0
+        flips = e.flipped_cells()
         got = e.read_packed()
     assert np.array_equal(got, want)
+    # the other half of the double buffer is the board exactly one turn back, after the join
+    # and the conversion: the flip list is the oracle's for this turn
+    yx = np.argwhere(oracle.unpack(prev, W) != oracle.unpack(want, W))
+    want_flips = np.ascontiguousarray(yx[:, ::-1].astype(np.int64))
+    assert len(want_flips) > 0
+    assert flips.shape == want_flips.shape and np.array_equal(flips, want_flips)
+
+
+SEAM_W = 1000                 # 15 words and 40 cells: the torus seam in x lies inside the last word
+
+
+@pytest.mark.parametrize("chunks", [2, 4, ALL])
+@pytest.mark.parametrize("h", HEIGHTS)
+@pytest.mark.parametrize("code", CODES)
+def test_seam_kernel_chunked(gol, oracle, monkeypatch, code, h, chunks):
+    """k_step_tile_seam under chunking (chunk_eligible does not exclude it, and large boards of
+    such widths reach it in automatic mode): 16 lane columns at tile width 13 leave a narrow
+    last column, repacked per chunk, and the chunks run the seam kernel with row_lo > 0 on a
+    torus that wraps.  Both codes are seam codes (gol_tile_seam_codes)."""
+    _pin(monkeypatch, code, chunks)
+    n = _fit(h, chunks)
+    assert n == (min(chunks, 5 if h == 203 else 7))
+    start, (want,) = _boards(oracle, h, (TURNS,), w=SEAM_W)
+    with _engine(gol, h, w=SEAM_W) as e:
+        assert e.info().fast_path == 0
+        e.load_packed(start)
+        e.step(TURNS)
+        assert [(k, v, b) for k, v, b in e.last_launches()] == [(k, 15, TH) for k in LAUNCHES]
+        assert {(a, b) for a, b, _ in e.last_launch_tiles()} == {(TW, code)}
+        assert e.last_step_chunks() == _expect(n)
+        assert e.info().launches == len(LAUNCHES) and e.info().turn == TURNS
+        got = e.read_packed()
+    assert np.array_equal(got, want)
+
+
+def test_two_words_per_lane_chunked(gol, oracle, monkeypatch):
+    """One two-words-per-lane code (1106) under chunking, at the tile shape test_tile_code_pinned
+    runs that family at (7 lanes x 100 rows): 21 lane columns are 3 tile columns; 430 rows are 4
+    tile rows and a 30-row one, so 4 chunks of 100, 100, 100 and 130 rows."""
+    code, tw, th, h = 1106, 7, 100, 430
+    monkeypatch.setenv("GOL_MULTI_VARIANT", "15")
+    monkeypatch.setenv("GOL_TILE", f"{tw},{code}")
+    monkeypatch.setenv("GOL_STEP_CHUNKS", "4")
+    assert _fit(h, 4, th=th) == 4
+    start, (want,) = _boards(oracle, h, (TURNS,))
+    with _engine(gol, h, th=th) as e:
+        e.load_packed(start)
+        e.step(TURNS)
+        assert [(k, v, b) for k, v, b in e.last_launches()] == [(k, 15, th) for k in LAUNCHES]
+        assert {(a, b) for a, b, _ in e.last_launch_tiles()} == {(tw, code)}
+        assert e.last_step_chunks() == 4 * 4
+        got = e.read_packed()
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("code", CODES)
+def test_nonbinary_load_then_chunked_step(gol, oracle, monkeypatch, code):
+    """A board loaded with a few bytes outside {0, 255}, then one chunked step: the first launch
+    is the one-turn masked launch, the pipeline starts behind it and behind the layout
+    conversion, and the mask is released after the join.  The 22 turns after the first spread
+    evenly over 4 launches: 6, 6, 5, 5."""
+    h = 203
+    start = _boards(oracle, h, (TURNS,))[0]
+    board = oracle.unpack(start, W).copy()
+    for y, x, v in ((0, 0, 1), (5, 17, 128), (39, 2687, 254), (40, 832, 7), (202, 1300, 200),
+                    (120, 63, 100), (121, 64, 3)):
+        board[y, x] = v
+    words, blocked, nb = oracle.pack(board)
+    assert nb == 7
+    want = oracle.bit_run(words, W, TURNS, blocked=blocked)
+    assert not np.array_equal(want, oracle.bit_run(words, W, TURNS))     # (the mask matters)
+    _pin(monkeypatch, code, 4)
+    with _engine(gol, h) as e:
+        e.load(board)
+        assert e.info().nonbinary_cells == 7
+        e.step(TURNS)
+        assert [(k, v) for k, v, _ in e.last_launches()] == [(1, 0), (6, 15), (6, 15), (5, 15),
+                                                             (5, 15)]
+        assert e.last_step_chunks() == 4 * 4
+        got = e.read_packed()
+        # (the mask is gone: a further one-turn step is an ordinary one)
+        e.step(1)
+        after = e.read_packed()
+    assert np.array_equal(got, want)
+    assert np.array_equal(after, oracle.bit_run(want, W, 1))
 
 
 def test_control_word_engine_is_not_chunked(gol, oracle, monkeypatch):

@@ -1,0 +1,550 @@
+"""gol_step's stream and event ordering on a host model of HIP: the unmodified csrc/gol_step.cpp
+linked with a stream-graph model of the HIP calls and kernel launches it leaves undefined
+(tests/harness/gol_stream_model.cpp) and driven by a stand-alone program
+(tests/harness/gol_step_hostcheck.cpp), built plain and with AddressSanitizer + UBSan
+(`make stepcheck`).  No GPU, no HIP runtime, nothing loaded into Python.
+
+The model checks every run two ways: a race check over happens-before (stream order, event
+edges, host flushes) against the rows each node really touched, and an execution of the pending
+nodes in a legal order chosen by a policy.  The verdicts here come from the oracle and from
+gol_step_chunk_plan, never from the program's own output: every policy's board is
+oracle.bit_run's, the counts are bit_run(..., counts=True)'s, the chunk counts are the plan's,
+and an unmutated run prints no RACE, no UNRECORDED_WAIT and no sanitizer report.  Mutated runs
+(GOL_MODEL_DROP_WAIT) must print a RACE: the negative control of DESIGN.md, "Negative controls".
+Boards and counts are exact; there is no tolerance anywhere.
+"""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "conway-s-gol-distributed_amd", "csrc")
+BIN = os.path.join(ROOT, "conway-s-gol-distributed_amd", "build", "hostcheck")
+BUILDS = ("plain", "asan")
+POLICIES = ("issue", "high", "low", "rand1", "rand2", "rand3")
+REPORT_MARKS = ("Sanitizer", "runtime error:")
+W, NW, TH, K, TURNS = 320, 5, 40, 6, 23
+LAUNCHES = [6, 6, 6, 5]
+KRING, KRING_AHEAD = 4096, 256
+KRING_SLOTS = KRING + KRING_AHEAD
+ALL = 64
+
+
+@pytest.fixture(scope="module")
+def stepcheck():
+    """`make stepcheck`: a no-op when the build is current; a failing build fails the tests."""
+    p = subprocess.run(["make", "-s", "-j", "2", "-C", CSRC, "stepcheck"], capture_output=True,
+                       text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    paths = {b: os.path.join(BIN, b, "gol_step_hostcheck") for b in BUILDS}
+    for path in paths.values():
+        assert os.path.exists(path), path
+    return paths
+
+
+# ------------------------------------------------------------------ expectations
+_RUNS = {}
+
+
+def boards(oracle, h, turns_list, seed=None):
+    """(start, boards after each cumulative turn count): computed once per key and shared;
+    callers do not modify them."""
+    key = (h, tuple(turns_list))
+    if key not in _RUNS:
+        start = oracle.gen_random(900 + h if seed is None else seed, W, h)
+        out, cur = [], start
+        for t in turns_list:
+            cur = oracle.bit_run(cur, W, t)
+            out.append(cur)
+        for a in [start] + out:
+            a.setflags(write=False)
+        _RUNS[key] = (start, out)
+    return _RUNS[key]
+
+
+def fit(rows, want, th=TH, min_rows=K):
+    """The chunks a launch on tiles of th rows gets when `want` are asked for and no chunk may
+    be shorter than min_rows (goleng::chunk_bounds through gol_step_chunk_plan)."""
+    from gol import _native as N
+    counts = (ctypes.c_int32 * 2)()
+    b0, b1 = (ctypes.c_int32 * (ALL + 1))(), (ctypes.c_int32 * (ALL + 1))()
+    deps = (ctypes.c_uint8 * (ALL * ALL))()
+    want = min(want, ALL)
+    assert N.lib().gol_step_chunk_plan(rows, min_rows, th, want, min_rows, th, want, counts, b0,
+                                       b1, deps, ALL) == 0
+    return counts[0]
+
+
+# ------------------------------------------------------------------ running the program
+class Run:
+    def __init__(self, policy):
+        self.policy = policy
+        self.streams = {}         # name -> id
+        self.waits = []           # (n, launch, stream, event_stream)
+        self.kernels = []         # dicts of the LAUNCH lines
+        self.races, self.unrecorded, self.steps, self.other = [], [], [], []
+        self.end = None
+
+    def chunks(self):
+        return [s["chunks"] for s in self.steps]
+
+
+def parse(out):
+    runs, run, step = [], None, None
+    for line in out.splitlines():
+        f = line.split()
+        if f[0] == "RUN":
+            run = Run(f[1])
+            runs.append(run)
+        elif f[0] == "STREAM":
+            run.streams[f[2]] = int(f[1])
+        elif f[0] == "WAIT":
+            kv = dict(x.split("=") for x in f[2:5])
+            run.waits.append((int(f[1]), int(kv["launch"]), int(kv["stream"]),
+                              int(kv["event_stream"])))
+        elif f[0] == "LAUNCH":
+            kv = dict(x.split("=") for x in f[2:])
+            lo, hi = kv.pop("rows").split("-")
+            d = {k: int(v) for k, v in kv.items()}
+            d.update(no=int(f[1]), lo=int(lo), hi=int(hi))
+            run.kernels.append(d)
+        elif f[0] == "RACE":
+            run.races.append(line)
+        elif f[0] == "UNRECORDED_WAIT":
+            run.unrecorded.append(line)
+        elif f[0] == "RC":
+            step = {"rc": int(f[1])}
+            run.steps.append(step)
+        elif f[0] == "CHUNKS":
+            step["chunks"] = int(f[1])
+        elif f[0] == "TURN":
+            step["turn"] = int(f[1])
+        elif f[0] == "LAUNCHES":
+            step["launches"] = [int(x) for x in f[1:]]
+        elif f[0] == "END":
+            run.end = dict((k, int(v)) for k, v in (x.split("=") for x in f[1:]))
+        else:
+            assert f[0] != "MODEL_ERROR", line
+            run.other.append(f)
+    return runs
+
+
+def run_program(binary, workdir, start, scenario, *args, chunks=None, drop=None, policy="all"):
+    np.ascontiguousarray(start, dtype=np.uint64).tofile(os.path.join(workdir, "in.bin"))
+    env = dict(os.environ)
+    for k in ("GOL_STEP_CHUNKS", "GOL_MODEL_DROP_WAIT"):
+        env.pop(k, None)
+    if chunks is not None:
+        env["GOL_STEP_CHUNKS"] = str(chunks)
+    if drop is not None:
+        env["GOL_MODEL_DROP_WAIT"] = drop
+    env["ASAN_OPTIONS"] = "detect_leaks=1"
+    env["UBSAN_OPTIONS"] = "print_stacktrace=1"
+    p = subprocess.run([binary, str(workdir), scenario, policy] + [str(a) for a in args],
+                       capture_output=True, text=True, env=env, timeout=60)
+    report = [m for m in REPORT_MARKS if m in p.stderr]
+    assert p.returncode == 0 and not report, (
+        f"{scenario} {' '.join(map(str, args))}: exit {p.returncode}\n{p.stdout[-2000:]}\n"
+        f"{p.stderr[-6000:]}")
+    runs = parse(p.stdout)
+    assert [r.policy for r in runs] == (list(POLICIES) if policy == "all" else [policy])
+    for r in runs:
+        assert r.end is not None and r.end["live_events"] == 0, r.end
+        assert r.end["races"] == len(r.races) and r.end["unrecorded"] == len(r.unrecorded)
+    return runs
+
+
+def read_board(workdir, policy, name, rows):
+    return np.fromfile(os.path.join(workdir, f"{policy}.{name}"), dtype=np.uint64).reshape(rows, NW)
+
+
+def check_clean(runs, workdir, files):
+    """The unmutated run: no race, no unrecorded wait, and under every policy every board file
+    is the oracle's.  files: {name: expected rows}."""
+    for r in runs:
+        assert r.races == [] and r.unrecorded == [], (r.policy, r.races[:5], r.unrecorded[:5])
+        for name, want in files.items():
+            got = read_board(workdir, r.policy, name, want.shape[0])
+            assert np.array_equal(got, want), (r.policy, name)
+    # every policy saw the same program: the waits and kernels do not depend on the order
+    for r in runs[1:]:
+        assert r.waits == runs[0].waits and r.kernels == runs[0].kernels
+
+
+def cross_waits(run, launch):
+    return [n for n, L, s, es in run.waits if L == launch and s != es]
+
+
+def drop_arg(ns):
+    return ",".join(str(n) for n in ns)
+
+
+# ------------------------------------------------------------------ S1: chunk counts
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("chunks", [1, 2, 3, 4, 5, ALL])
+@pytest.mark.parametrize("h", (203, 270))
+def test_s1_chunk_counts(stepcheck, oracle, tmp_path, build, h, chunks):
+    """The GPU test's shapes (tests/test_gpu_step_chunks.py::test_chunk_counts) at 320 cells."""
+    n = fit(h, chunks)
+    assert n == min(chunks, 5 if h == 203 else 7)
+    start, (want,) = boards(oracle, h, (TURNS,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s1", h, TURNS, K, chunks=chunks)
+    check_clean(runs, tmp_path, {"board": want})
+    for r in runs:
+        assert r.steps == [{"rc": 0, "chunks": len(LAUNCHES) * n if n > 1 else 0, "turn": TURNS,
+                            "launches": LAUNCHES}]
+        assert len(r.kernels) == len(LAUNCHES) * n
+        # the chunks of every launch tile the board, on both streams when there are several
+        for i in range(len(LAUNCHES)):
+            ks = sorted((k["lo"], k["hi"]) for k in r.kernels if k["launch"] == i)
+            assert ks[0][0] == 0 and ks[-1][1] == h and all(a[1] == b[0] for a, b in zip(ks, ks[1:]))
+            assert len({k["stream"] for k in r.kernels if k["launch"] == i}) == min(n, 2)
+
+
+def _chunked_launch_mutations(binary, tmp_path, start, scenario, args, chunks, launches):
+    """Drop together the cross-stream waits issued during each chunked launch after the first:
+    every such run races.  Then every wait singly: at least one per chunked launch races.
+    Returns the single-drop table [(wait, launch, stream, event_stream, races)]."""
+    base = run_program(binary, tmp_path, start, scenario, *args, chunks=chunks, policy="issue")[0]
+    assert base.races == []
+    table = []
+    for i in launches:
+        ns = cross_waits(base, i)
+        assert ns, f"launch {i} issued no cross-stream wait"
+        r = run_program(binary, tmp_path, start, scenario, *args, chunks=chunks, policy="issue",
+                        drop=drop_arg(ns))[0]
+        assert r.races, f"launch {i}: waits {ns} dropped and no race"
+    for n, L, s, es in base.waits:
+        r = run_program(binary, tmp_path, start, scenario, *args, chunks=chunks, policy="issue",
+                        drop=str(n))[0]
+        assert r.unrecorded == []
+        table.append((n, L, s, es, len(r.races)))
+    for i in launches:
+        assert any(races for n, L, s, es, races in table if L == i and s != es), i
+    return table
+
+
+@pytest.mark.parametrize("h,chunks,n", [(203, 4, 4), (203, 5, 5), (270, 4, 4), (270, 5, 5),
+                                        (270, ALL, 7)])
+def test_s1_dropped_waits_race(stepcheck, oracle, tmp_path, h, chunks, n):
+    """4, 5 and 7 chunks: the cases where a chunk follows only its neighbours, which pass on a
+    GPU with the waits removed."""
+    assert fit(h, chunks) == n
+    start, _ = boards(oracle, h, (TURNS,))
+    _chunked_launch_mutations(stepcheck["plain"], tmp_path, start, "s1", (h, TURNS, K), chunks,
+                              (1, 2, 3))
+
+
+def test_s1_dropped_waits_wrong_board(stepcheck, oracle, tmp_path):
+    """The model's second check sees the same mutation: with the cross-stream waits of launch 2
+    dropped at 5 chunks, some policy computes another board than the oracle's."""
+    h = 270
+    start, (want,) = boards(oracle, h, (TURNS,))
+    base = run_program(stepcheck["plain"], tmp_path, start, "s1", h, TURNS, K, chunks=5,
+                       policy="issue")[0]
+    runs = run_program(stepcheck["plain"], tmp_path, start, "s1", h, TURNS, K, chunks=5,
+                       drop=drop_arg(cross_waits(base, 2)))
+    assert all(r.races for r in runs)
+    assert not all(np.array_equal(read_board(tmp_path, r.policy, "board", h), want) for r in runs)
+
+
+# ------------------------------------------------------------------ S2: mixed shapes
+S2_LAUNCHES = [(6, 40), (5, 48), (6, 32)]
+
+
+def _s2_chunks(want):
+    total = 0
+    for i, (k, th) in enumerate(S2_LAUNCHES):
+        near = [S2_LAUNCHES[j][0] for j in (i - 1, i, i + 1) if 0 <= j < len(S2_LAUNCHES)]
+        total += fit(640, want, th=th, min_rows=max(near))
+    return total
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("chunks", (4, 8))
+@pytest.mark.parametrize("mode", ("seq", "plan"))
+def test_s2_mixed_shapes(stepcheck, oracle, tmp_path, build, mode, chunks):
+    """Consecutive launches of different depth and tile height, from shape.seq and from
+    shape.plan: the chunk bounds of neighbouring launches do not line up."""
+    start, (want,) = boards(oracle, 640, (17,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s2", mode, chunks=chunks)
+    check_clean(runs, tmp_path, {"board": want})
+    for r in runs:
+        assert r.steps == [{"rc": 0, "chunks": _s2_chunks(chunks), "turn": 17,
+                            "launches": [k for k, _ in S2_LAUNCHES]}]
+        for i, (k, th) in enumerate(S2_LAUNCHES):
+            ks = [x for x in r.kernels if x["launch"] == i]
+            assert len(ks) == chunks and all(x["k"] == k for x in ks)
+            assert all(x["lo"] % th == 0 for x in ks)
+
+
+@pytest.mark.parametrize("chunks", (4, 8))
+@pytest.mark.parametrize("mode", ("seq", "plan"))
+def test_s2_dropped_waits_race(stepcheck, oracle, tmp_path, mode, chunks):
+    start, _ = boards(oracle, 640, (17,))
+    _chunked_launch_mutations(stepcheck["plain"], tmp_path, start, "s2", (mode,), chunks, (1, 2))
+
+
+# ------------------------------------------------------------------ S3: automatic mode
+def _auto_want(rows, ncu):
+    """chunks_wanted with GOL_STEP_CHUNKS unset, on the model's grid (one tile column, one
+    resident workgroup per CU): at least 4 rounds of workgroups, chunks of about 2 rounds."""
+    wg, slots = -(-rows // TH), ncu
+    if wg < 4 * slots:
+        return 1
+    return min(ALL, max(2, int(wg / (2.0 * slots) + 0.5)))
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("rows,ncu,want", [(640, 4, 2), (640, 2, 4), (640, 1, 8), (600, 4, 1),
+                                           (600, 3, 3)])
+def test_s3_automatic_mode(stepcheck, oracle, tmp_path, build, rows, ncu, want):
+    """GOL_STEP_CHUNKS unset: chunks_wanted decides.  600 rows on 4 CUs are 15 workgroups, one
+    short of 4 rounds: the launches stay whole."""
+    assert _auto_want(rows, ncu) == want
+    n = fit(rows, want)
+    assert n == want
+    start, (board,) = boards(oracle, rows, (TURNS,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s3", rows, TURNS, K, ncu)
+    check_clean(runs, tmp_path, {"board": board})
+    for r in runs:
+        assert r.steps == [{"rc": 0, "chunks": 4 * n if n > 1 else 0, "turn": TURNS,
+                            "launches": LAUNCHES}]
+
+
+# ------------------------------------------------------------------ S4: joins
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("chunks", (4, 5))
+def test_s4_step_ends_in_one_turn_launch(stepcheck, oracle, tmp_path, build, chunks):
+    """5 turns at 2 per launch: 2, 2, 1.  The layout conversion and the one-turn launch meet a
+    live pipeline inside the step."""
+    h = 203
+    n = fit(h, chunks, min_rows=2)
+    assert n == chunks
+    start, (want,) = boards(oracle, h, (5,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s4", "tail", chunks=chunks)
+    check_clean(runs, tmp_path, {"board": want})
+    for r in runs:
+        assert r.steps == [{"rc": 0, "chunks": 2 * n, "turn": 5, "launches": [2, 2, 1]}]
+        assert [x["k"] for x in r.kernels if x["launch"] == 2] == [1]
+
+
+@pytest.mark.parametrize("chunks", (4, 5))
+def test_s4_dropped_join_races(stepcheck, oracle, tmp_path, chunks):
+    """The join in front of the one-turn launch (the engine stream's waits for the side chunks
+    of launch 1, issued when launch 2 is about to go out) dropped: a race."""
+    start, _ = boards(oracle, 203, (5,))
+    base = run_program(stepcheck["plain"], tmp_path, start, "s4", "tail", chunks=chunks,
+                       policy="issue")[0]
+    side, eng = base.streams["side"], base.streams["engine"]
+    join = [n for n, L, s, es in base.waits if L == 2 and s == eng and es == side]
+    # (the stream alternation carries on across launches: launch 1's chunks are the 4th .. 7th,
+    # or 5th .. 9th, issued since the pipeline went live, the odd ones on the side stream)
+    assert len(join) == sum(i & 1 for i in range(chunks, 2 * chunks))
+    r = run_program(stepcheck["plain"], tmp_path, start, "s4", "tail", chunks=chunks,
+                    policy="issue", drop=drop_arg(join))[0]
+    assert r.races
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_s4_steps_back_to_back(stepcheck, oracle, tmp_path, build):
+    """Two chunked steps with a host read between them and different chunk counts."""
+    h = 270
+    start, (mid, want) = boards(oracle, h, (TURNS, 2 * K))
+    runs = run_program(stepcheck[build], tmp_path, start, "s4", "two", chunks=3)
+    check_clean(runs, tmp_path, {"mid.board": mid, "board": want})
+    for r in runs:
+        assert r.chunks() == [4 * fit(h, 3), 2 * fit(h, 5)] == [12, 10]
+        assert [s["launches"] for s in r.steps] == [LAUNCHES, [K, K]]
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_s4_one_turn_step_after_chunks(stepcheck, oracle, tmp_path, build):
+    """A chunked step, then a step of one turn: the other half of the double buffer is the
+    board exactly one turn back, in the standard layout."""
+    h = 203
+    start, (prev, want) = boards(oracle, h, (TURNS, 1))
+    runs = run_program(stepcheck[build], tmp_path, start, "s4", "one", chunks=4)
+    check_clean(runs, tmp_path, {"board": want, "prev.board": prev})
+    for r in runs:
+        assert r.chunks() == [16, 0] and r.steps[1]["launches"] == [1]
+        assert ["PREV_VALID", "1"] in r.other
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_s4_lone_launch_stays_whole(stepcheck, oracle, tmp_path, build):
+    h = 203
+    start, (want,) = boards(oracle, h, (K,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s4", "lone", chunks=4)
+    check_clean(runs, tmp_path, {"board": want})
+    for r in runs:
+        assert r.steps == [{"rc": 0, "chunks": 0, "turn": K, "launches": [K]}]
+        assert len(r.kernels) == 1 and r.waits == []
+
+
+# ------------------------------------------------------------------ S5, S6: mid-step
+@pytest.mark.parametrize("build", BUILDS)
+def test_s5_reader_mid_step(stepcheck, oracle, tmp_path, build):
+    """A reader's job posted while launch 2 of 4 goes out: it is served before launch 3, reads
+    the board at c->turn = 18 on the engine stream, and the rest of the step runs unchunked."""
+    h = 270
+    start, (at18, want) = boards(oracle, h, (18, 5))
+    runs = run_program(stepcheck[build], tmp_path, start, "s5", chunks=4)
+    check_clean(runs, tmp_path, {"job.board": at18, "board": want})
+    for r in runs:
+        assert ["JOB", "turn=18", "launches=3"] in r.other and ["JOBDONE", "1", "rc=0"] in r.other
+        assert r.steps == [{"rc": 0, "chunks": 3 * fit(h, 4), "turn": TURNS, "launches": LAUNCHES}]
+        assert [len([x for x in r.kernels if x["launch"] == i]) for i in range(4)] == [4, 4, 4, 1]
+        # the last launch and the reader's copy are on the engine stream
+        assert [x["stream"] for x in r.kernels if x["launch"] == 3] == [r.streams["engine"]]
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_s6_control_word(stepcheck, oracle, tmp_path, build):
+    """A controlled engine never chunks; STOP stored while launch 2 goes out returns GOL_STOPPED
+    before launch 3 with the board complete at c->turn."""
+    h = 270
+    start, (at18,) = boards(oracle, h, (18,))
+    runs = run_program(stepcheck[build], tmp_path, start, "s6", chunks=4)
+    check_clean(runs, tmp_path, {"board": at18})
+    for r in runs:
+        assert r.steps == [{"rc": 1, "chunks": 0, "turn": 18, "launches": [6, 6, 6]}]
+        assert len(r.kernels) == 3 and not [w for w in r.waits if w[2] != w[3]]
+
+
+# ------------------------------------------------------------------ S7: gol_step_overlap
+HALO = 11
+# form -> (rows per strip, the windows' turns, kernels of each window's first launch by stream)
+S7 = {
+    "multi": (40, [11, 11], ["engine", "side", "side"]),
+    "one": (40, [1, 1], ["engine", "side", "side"]),
+    "short": (12, [6, 6], ["side"]),
+    "ilone": (40, [11, 1, 1], None),
+    "count": (40, [11, 11], ["engine"]),
+}
+
+
+def _s7_input(oracle, form):
+    rows, windows, _ = S7[form]
+    h = 2 * rows
+    start, after = boards(oracle, h, tuple(windows), seed=7000 + h)
+    truth = [start] + after[:-1]                  # the board at every window's first turn
+    return h, np.concatenate(truth), start, after[-1]
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("form", sorted(S7))
+def test_s7_overlap(stepcheck, oracle, tmp_path, build, form):
+    """Two strips with 11-row halos; the receives are nodes on a third stream that write the
+    halo rows with the true rows.  The policy that runs the highest stream last runs them as late
+    as the waits allow.  Each strip's owned rows are the oracle's after the last window."""
+    rows, windows, first = S7[form]
+    h, truth, start, want = _s7_input(oracle, form)
+    runs = run_program(stepcheck[build], tmp_path, truth, "s7", form, 2, *windows)
+    files = {f"s{i}.board": want[i * rows:(i + 1) * rows] for i in range(2)}
+    check_clean(runs, tmp_path, files)
+    for r in runs:
+        assert [s["rc"] for s in r.steps] == [0] * (2 * len(windows))
+        assert [s["turn"] for s in r.steps] == list(np.cumsum(windows)) * 2
+        if first:
+            for i in range(2):
+                name = {v: k for k, v in r.streams.items()}
+                ks = [x for x in r.kernels if name[x["stream"]].startswith(f"s{i}.")]
+                launch0 = [name[x["stream"]].split(".")[1] for x in ks if x["launch"] == 0]
+                assert launch0 == first
+        if form == "count":
+            turns = sum(windows)
+            for i in range(2):
+                got = {int(f[1]): int(f[2]) for f in r.other if f[0] == f"COUNT{i}"}
+                cur, expect = start, {}
+                for t in range(1, turns + 1):
+                    cur = oracle.bit_run(cur, W, 1)
+                    expect[t] = oracle.popcount(cur[i * rows:(i + 1) * rows], W)
+                assert got == expect
+
+
+@pytest.mark.parametrize("form", sorted(S7))
+def test_s7_dropped_receive_waits_race(stepcheck, oracle, tmp_path, form):
+    """Every wait for the receive stream, dropped singly, is a race -- except where the window
+    issues two of them (a one-turn window on an interleaved board: the conversion on the engine
+    stream waits for the receives, and the side stream, which starts behind the engine stream,
+    waits for them again): there the second one is covered by the first, and dropping both
+    races."""
+    rows, windows, _ = S7[form]
+    h, truth, _, _ = _s7_input(oracle, form)
+
+    def run(drop=None):
+        return run_program(stepcheck["plain"], tmp_path, truth, "s7", form, 2, *windows,
+                           policy="issue", drop=drop)[0]
+
+    base = run()
+    recv = {v for k, v in base.streams.items() if k.endswith(".recv")}
+    # (wait, the launch it was issued at, the receive stream waited for)
+    ns = [(n, L, es) for n, L, s, es in base.waits if es in recv]
+    assert len(ns) >= 2 * len(windows)            # at least one per window and strip
+    seen = {n: bool(run(str(n)).races) for n, _, _ in ns}
+    if form != "ilone":
+        assert all(seen.values()), seen
+        return
+    # window by window: the waits for one receive stream issued at one launch
+    groups = {}
+    for n, L, es in ns:
+        groups.setdefault((es, L), []).append(n)
+    assert sorted(len(g) for g in groups.values()) == [1, 1, 2, 2, 2, 2]
+    for key, g in groups.items():
+        assert run(drop_arg(g)).races, (key, g)
+        assert seen[g[0]], (key, g)               # the first of a window is never covered
+
+
+# ------------------------------------------------------------------ S8: the count ring
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("turn0", (3 * KRING_AHEAD - 4, KRING_SLOTS - 5))
+def test_s8_count_ring(stepcheck, oracle, tmp_path, build, turn0):
+    """A counted engine a few turns below a multiple of kRingAhead (the memsets of
+    zero_count_slots straddle a batch) and below kRingSlots (plan_launch stops a launch at the
+    ring's end).  The per-turn counts are the oracle's, and a job served mid-step sees no zeroed
+    slot for a turn inside the window gol_turn_counts accepts."""
+    h = 203
+    start, _ = boards(oracle, h, (TURNS,))
+    want, wc = oracle.bit_run(start, W, TURNS, counts=True)
+    runs = run_program(stepcheck[build], tmp_path, start, "s8", turn0, TURNS, chunks=4)
+    check_clean(runs, tmp_path, {"board": want})
+    expect = {turn0 + 1 + i: int(c) for i, c in enumerate(wc)}
+    for r in runs:
+        (step,) = r.steps
+        assert step["rc"] == 0 and step["chunks"] == 0 and step["turn"] == turn0 + TURNS
+        assert sum(step["launches"]) == TURNS
+        # no launch's slots wrap the ring: a launch covers turns (t, t + k], slots consecutive
+        t = turn0
+        for k in step["launches"]:
+            assert (t + 1) % KRING_SLOTS + k <= KRING_SLOTS, step["launches"]
+            t += k
+        assert all(x["counts"] == 1 for x in r.kernels)
+        got = {int(f[1]): int(f[2]) for f in r.other if f[0] == "COUNT"}
+        assert got == expect
+        job = [f for f in r.other if f[0] == "JOB"]
+        assert len(job) == 1
+        jt = int(job[0][1].split("=")[1])
+        assert turn0 < jt < turn0 + TURNS and job[0][2] == "launches=3"
+        assert not [f for f in r.other if f[0] == "JOBZERO"]
+        lo = max(0, jt - KRING + 1)
+        assert job[0][3] == f"window={lo}-{jt}" and job[0][4] == f"nonzero={jt - lo + 1}"
+        seen = {int(f[1]): int(f[2]) for f in r.other if f[0] == "JOBCOUNT"}
+        assert seen == {t: v for t, v in expect.items() if t <= jt}
+
+
+# ------------------------------------------------------------------ the binaries
+def test_binaries_link_no_hip_and_no_shared_sanitizer(stepcheck):
+    """No undefined hip* symbol, no HIP runtime and no shared sanitizer runtime."""
+    for path in stepcheck.values():
+        nm = subprocess.run(["nm", "-u", path], capture_output=True, text=True, check=True).stdout
+        assert not [ln for ln in nm.splitlines() if " hip" in ln.lower()], nm
+        dyn = subprocess.run(["readelf", "-d", path], capture_output=True, text=True,
+                             check=True).stdout
+        needed = [ln.split("[", 1)[1].rstrip("]") for ln in dyn.splitlines() if "(NEEDED)" in ln]
+        assert any(n.startswith("libc.so") for n in needed), dyn
+        for lib in ("amdhip", "libhsa", "libtsan", "libasan", "libubsan", "libclang_rt"):
+            assert not [n for n in needed if lib in n], dyn
