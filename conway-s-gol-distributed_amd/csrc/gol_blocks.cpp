@@ -1,7 +1,8 @@
 // gol_blocks.cpp — the host side of K1p / K1q / K1r (k_tile_persist, k_tile_stream,
 // k_tile_ring): many blocks of turns in one launch, tiles handing their edges over through
 // uncached buffers.  The kernels exist in the tools build only (make tools, -DGOL_TOOLS=1); the
-// product library gets the stubs at the end of this file.
+// product library gets the stubs at the end of this file.  Also tools-only: the k_step_wg wait
+// diagnostic launch (wg_diag_launch).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -323,6 +324,61 @@ void blocks_free(gol_ctx *c)
         if (u) (void)hipFree(u);
     if (b.pcounter) (void)hipFree(b.pcounter);
     if (b.pflags) (void)hipFree(b.pflags);
+}
+
+// GOL_MULTI_VARIANT=kMultiWgDiag: one k_step_wg launch with per-wave wait timing, summarised by
+// wave role on stderr (tools/wg_diag.py reads the lines).
+int wg_diag_launch(gol_ctx *c, golk::StepArgs a, int k)
+{
+    const long long ntx = golk::multi_tiles(c->cfg.width, 2);
+    const long long pipes = ntx * ((a.row_hi - a.row_lo + a.band - 1) / a.band);
+    const size_t n = (size_t)pipes * 4 * 10;
+    unsigned long long *d = nullptr;
+    HIP_OR_FAIL(c, hipMalloc(&d, n * 8));
+    HIP_OR_FAIL(c, hipMemsetAsync(d, 0, n * 8, c->stream));
+    a.counts = d;
+    HIP_OR_FAIL(c, golk::launch_step_multi(a, k, c->stream));
+    std::vector<unsigned long long> h(n);
+    HIP_OR_FAIL(c, hipMemcpyAsync(h.data(), d, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(d);
+    unsigned long long t0min = ~0ull, t1max = 0;
+    std::vector<unsigned long long> starts, ends;        // wave 0's start / wave 3's end
+    for (long long p = 0; p < pipes; ++p)
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long *e = &h[((size_t)p * 4 + w) * 10];
+            if (e[8] == 0) continue;                     // a workgroup past the last band
+            t0min = std::min(t0min, e[8]);
+            t1max = std::max(t1max, e[9]);
+            if (w == 0) starts.push_back(e[8]);
+            if (w == 3) ends.push_back(e[9]);
+        }
+    auto pct = [](std::vector<unsigned long long> v, unsigned long long base, double q) {
+        if (v.empty()) return 0.0;
+        std::sort(v.begin(), v.end());
+        return (double)(v[(size_t)(q * (double)(v.size() - 1))] - base);
+    };
+    fprintf(stderr,
+            "wg_diag starts (100 MHz ticks after the first) p10 %.0f p50 %.0f p90 %.0f max %.0f; "
+            "ends p10 %.0f p50 %.0f p90 %.0f max %.0f\n",
+            pct(starts, t0min, 0.1), pct(starts, t0min, 0.5), pct(starts, t0min, 0.9),
+            pct(starts, t0min, 1.0), pct(ends, t0min, 0.1), pct(ends, t0min, 0.5),
+            pct(ends, t0min, 0.9), pct(ends, t0min, 1.0));
+    for (int w = 0; w < 4; ++w) {
+        double life = 0, first = 0, fw = 0, nf = 0, ew = 0, ne = 0, nl = 0;
+        for (long long p = 0; p < pipes; ++p) {
+            const unsigned long long *e = &h[((size_t)p * 4 + w) * 10];
+            life += (double)e[0]; first += (double)e[1]; fw += (double)e[2];
+            nf += (double)e[3]; ew += (double)e[4]; ne += (double)e[5]; nl += (double)e[6];
+        }
+        fprintf(stderr,
+                "wg_diag K=%d band=%d pipes=%lld wave %d: life %.0f ticks, first-row wait %.1f%%, "
+                "fetch waits %.1f%% (%.2f per row), emit waits %.1f%% (%.2f per row)\n",
+                k, a.band, pipes, w, life / pipes, 100 * first / life, 100 * fw / life, nf / nl,
+                100 * ew / life, ne / nl);
+    }
+    fprintf(stderr, "wg_diag launch span %llu ticks of 100 MHz\n", t1max - t0min);
+    return GOL_OK;
 }
 
 #else  // the product library: no K1p / K1q / K1r kernels

@@ -4,10 +4,14 @@
 //   gol_engine.cpp   create / destroy, info, the pinned-shape table and its check, the
 //                    per-device engine registry, errors
 //   gol_tune.cpp     the k_step_tile model and search, the create-time autotune, the tune cache
-//   gol_step.cpp     the launch planner, gol_step / gol_step_overlap, the read-job queue
+//   gol_plan.cpp     the launch planner (kernel, depth, band, row chunks) and the calls that
+//                    report plans and tables; no stream or event call
+//   gol_step.cpp     gol_step / gol_step_overlap: launches, stream and event ordering, the chunk
+//                    pipeline, the read-job queue, the control word
 //   gol_io.cpp       load, read-out, counts, alive and flip lists
 //   gol_halo.cpp     halo exchange
-//   gol_blocks.cpp   K1p / K1q / K1r host side (tools build; stubs in the product)
+//   gol_blocks.cpp   K1p / K1q / K1r host side and the k_step_wg wait diagnostic (tools build;
+//                    stubs in the product)
 //
 // One gol_ctx = one MI355X holding either the whole torus board or one row
 // strip of it (the reference's SubServer strip, Server/gol/distributor.go:
@@ -304,7 +308,7 @@ struct LaunchTimer {
     }
 };
 
-// ---------------------------------------------------------------- gol_step.cpp
+// ---------------------------------------------------------------- gol_plan.cpp
 // The only place an engine's launch shape is assigned (it resets the per-depth band cache).
 void set_shape(gol_ctx *c, LaunchShape s);
 // StepArgs for the whole buffer on the engine's stream: everything but the kernel choice
@@ -313,8 +317,9 @@ golk::StepArgs whole_buffer_args(const gol_ctx *c);
 int band_same_rounds(const gol_ctx *c, int var, int K0, int band0, int k);
 Launch plan_launch(gol_ctx *c, int64_t room);
 bool stepping_il(const gol_ctx *c, int k);
-int ensure_layout(gol_ctx *c, bool il);
-hipError_t pg_prepare(gol_ctx *c, golk::StepArgs &a, int k);
+// the launch sequence the autotune timed for a torus gol_step of exactly `turns` turns
+// (shape.seq), or null: follow plan_launch
+const std::vector<Launch> *timed_sequence(const gol_ctx *c, int64_t turns);
 // Row chunks of one k_step_tile launch over `rows` buffer rows on tiles of tile_h rows: the
 // n + 1 bounds of n <= want chunks, cut on multiples of tile_h (the tile rows spread evenly:
 // floor(tile rows / n) each, one more for the last tile rows % n chunks; the ragged tile row
@@ -325,6 +330,20 @@ std::vector<int> chunk_bounds(int rows, int tile_h, int want, int min_rows);
 // one (bounds nb, depth kn) must follow on the torus of `rows` buffer rows
 std::vector<std::vector<int>> chunk_deps(int rows, const std::vector<int> &pb, int kp,
                                          const std::vector<int> &nb, int kn);
+// Chunks per launch of one gol_step call, read once per call: 1 = never (GOL_STEP_CHUNKS=1, and
+// every call that cannot chunk: strip and count engines, a control word in use, an overlapped
+// window, no side stream), n >= 2 = n chunks (GOL_STEP_CHUNKS=n), -1 = automatic (unset / 0)
+int chunk_request(const gol_ctx *c, bool ctl, bool overlapped);
+// The chunk bounds of launch L under `request` (empty: one whole kernel).  A launch is cut when
+// the one before it was (k_live: the depth of the live pipeline's last launch, else 0) or when
+// the next one can be -- timed_next, or else plan_launch's for the `left` turns after L; a lone
+// launch stays whole.  Every chunk is at least as tall as L's and both neighbours' depths.
+std::vector<int> plan_chunks(gol_ctx *c, const Launch &L, int request, int64_t left,
+                             const Launch *timed_next, int k_live);
+
+// ---------------------------------------------------------------- gol_step.cpp
+int ensure_layout(gol_ctx *c, bool il);
+hipError_t pg_prepare(gol_ctx *c, golk::StepArgs &a, int k);
 
 // ---------------------------------------------------------------- gol_io.cpp
 void release_blocked(gol_ctx *c);
@@ -382,5 +401,9 @@ bool blocks_plan(gol_ctx *c, int64_t room, Launch *out);
 // one launch of kind kMultiTilePersist / kMultiTileStream
 hipError_t blocks_launch(gol_ctx *c, const golk::StepArgs &a, const Launch &L);
 void blocks_free(gol_ctx *c);
+#if GOL_TOOLS
+// GOL_MULTI_VARIANT=kMultiWgDiag: one k_step_wg launch of `a` with per-wave wait timing
+int wg_diag_launch(gol_ctx *c, golk::StepArgs a, int k);
+#endif
 
 }  // namespace goleng

@@ -1,9 +1,9 @@
 // gol_stream_model.cpp -- a host model of the HIP streams and events and of the kernel launch
-// interface that csrc/gol_step.cpp leaves undefined, so the unmodified planner / gol_step /
-// gol_step_overlap source links into a host-only program (tests/harness/gol_step_hostcheck.cpp;
-// csrc/Makefile `stepcheck`, tests/test_step_host_cpu.py).  No HIP runtime, one thread.  Test
-// infrastructure only: it stands for what ORDERS the kernels, not for the kernels (DESIGN.md
-// "gol_step under a stream model").
+// interface that csrc/gol_step.cpp and csrc/gol_plan.cpp leave undefined, so the unmodified
+// planner / gol_step / gol_step_overlap source links into a host-only program (tests/harness/
+// gol_step_hostcheck.cpp; csrc/Makefile `stepcheck`, tests/test_step_host_cpu.py).  No HIP
+// runtime, one thread.  Test infrastructure only: it stands for what ORDERS the kernels, not for
+// the kernels (DESIGN.md "gol_step under a stream model").
 //
 // Streams, events, waits.  A stream is a queue of nodes; nothing runs when it is enqueued.
 // hipEventRecord(e, s) binds e to the last node of s at that moment (to a marker node when s is

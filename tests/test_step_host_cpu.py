@@ -1,5 +1,5 @@
 """gol_step's stream and event ordering on a host model of HIP: the unmodified csrc/gol_step.cpp
-linked with a stream-graph model of the HIP calls and kernel launches it leaves undefined
+(and its planner csrc/gol_plan.cpp) linked with a stream-graph model of the HIP calls and kernel launches it leaves undefined
 (tests/harness/gol_stream_model.cpp) and driven by a stand-alone program
 (tests/harness/gol_step_hostcheck.cpp), built plain and with AddressSanitizer + UBSan
 (`make stepcheck`).  No GPU, no HIP runtime, nothing loaded into Python.
