@@ -135,6 +135,11 @@ struct gol_ctx {
     // at a golk::kTileSeamCodes code when width % 64 != 0.  (Off for forced-generic and count
     // engines, and under a GOL_MULTI_VARIANT other than k_step_tile: one turn per launch.)
     bool tile_only = false;
+    // the engine's k_step_tile launches run the big form (k_step_tile_big): a buffer of 2 GiB or
+    // more on whole-word rows of >= 256 cells (then also tile_only: no other kernel blocks such
+    // a buffer), or GOL_TILE_BIG=1 at create on a buffer of any size.  tile_big_forced: the
+    // latter, which also goes to the launches (StepArgs::tile_big)
+    bool tile_big = false, tile_big_forced = false;
     int band = 8;
     int variant = golk::kVariantDefault;
     int multi_words = 2;                     // k_step_multi words per lane
@@ -175,7 +180,9 @@ struct gol_ctx {
     long long turn = 0;
     long long launches = 0;
     int halo_valid = 0;
-    bool blocking_limited = false;           // temporal blocking off: buffer >= 2 GiB
+    // temporal blocking off: a buffer of 2 GiB or more that the big form does not run (a count
+    // engine, width % 64 != 0, width < 256, forced-generic, another GOL_MULTI_VARIANT)
+    bool blocking_limited = false;
     // GOL_FLAG_COUNT_EVERY_TURN engines: multi-turn launches with the counts fused into
     // k_step_tile are allowed (GOL_COUNT_BLOCKING=0 at create: one-turn launches, for A/B)
     bool count_blocking = false;
@@ -355,8 +362,10 @@ struct TileShape {
 };
 // (width: the board's when its width is no multiple of 64 -- golk::tile_shape_ok; else 0)
 double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg, int width = 0);
+// (big: for an engine that runs the big form on a buffer of `rows` rows of nw words -- codes of
+// golk::kTileBigCodes and tile heights whose window it takes)
 std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt = false,
-                                       int width = 0);
+                                       int width = 0, bool big = false);
 // the engine runs k_step_tile at this shape (no plan, no K1p; K1q's shape and the measured time
 // stay)
 void apply_tile(gol_ctx *c, const TileShape &t);

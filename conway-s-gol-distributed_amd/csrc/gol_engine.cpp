@@ -172,7 +172,8 @@ bool known_shape(const gol_ctx *c, KnownShape *out)
         return false;
     for (const KnownShape &k : kKnownShapes)
         if (k.width == c->cfg.width && k.rows == c->buf_rows &&
-            golk::tile_shape_ok(c->nw, k.t.K, k.t.th, k.t.tw, k.t.seg)) {
+            golk::tile_shape_ok(c->nw, k.t.K, k.t.th, k.t.tw, k.t.seg) &&
+            (!c->tile_big || golk::tile_big_ok(k.width, c->buf_rows, c->pitch, k.t.K, k.t.th, k.t.seg))) {
             *out = k;
             return true;
         }
@@ -305,7 +306,15 @@ int initial_tile_shape(gol_ctx *c, bool cntb)
     if (const char *v = getenv("GOL_TURNS_PER_LAUNCH"))
         K = std::max(2, std::min(atoi(v), golk::kMaxTileTurns));
     std::vector<TileShape> cand =
-        tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20, cntb, c->cfg.width);
+        tile_candidates(c->ncu, c->nw, c->buf_rows, 1 << 20, cntb, c->cfg.width, c->tile_big);
+    // a big engine starts from the 65536^2 pins (kKnownShapes: 30 lanes x 452 rows at K = 30,
+    // 30 x 472 at K = 20, ORD 5 SEG 16 in 16-wave workgroups) where they run: rows as long and
+    // a buffer as tall as that board's or more
+    if (c->tile_big)
+        for (const TileShape &t : {TileShape{20, 472, 30, 516, 0}, TileShape{30, 452, 30, 516, 0}})
+            if (golk::tile_shape_ok(c->nw, t.K, t.th, t.tw, t.seg, c->cfg.width) &&
+                golk::tile_big_ok(c->cfg.width, c->buf_rows, c->pitch, t.K, t.th, t.seg))
+                cand.insert(cand.begin(), t);
     for (const TileShape &t : cand)
         if (K == 0 || t.K == K) {
             apply_tile(c, t);
@@ -333,6 +342,11 @@ int initial_tile_shape(gol_ctx *c, bool cntb)
     }
     if (s.multi_variant == golk::kMultiTile &&
         !golk::tile_shape_ok(c->nw, s.tpl, s.band_multi, s.tile_w, s.tile_seg, c->cfg.width))
+        return GOL_EINVAL;
+    // the big form: a code of its set, a window that wraps at most once and stays below 2 GiB
+    if (c->tile_big && (s.multi_variant != golk::kMultiTile ||
+                        !golk::tile_big_ok(c->cfg.width, c->buf_rows, c->pitch, s.tpl, s.band_multi,
+                                           s.tile_seg)))
         return GOL_EINVAL;
     if (int rc = blocks_parse_env(c)) return rc;   // GOL_PERSIST / GOL_RING / GOL_STREAM
     // (K1p / K1q / K1r know nothing of the row seam or of odd word counts)
@@ -423,6 +437,20 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     // it has no counted form across the seam, and they keep one rule at all these widths)
     c->tile_only = !golk::fast_path_ok(cfg->width) && cfg->width >= 256 && c->multi_words == 1 &&
                    !(cfg->flags & (GOL_FLAG_FORCE_GENERIC | GOL_FLAG_COUNT_EVERY_TURN));
+    // a buffer of 2 GiB or more: the big form of K1t alone blocks it, on whole-word rows of >= 256
+    // cells and with no counts (it has neither a seam nor a counted form).  GOL_TILE_BIG=1 (tests,
+    // A/B runs) forces the form on a buffer of any size, and fails the create where it cannot run.
+    const char *tb = getenv("GOL_TILE_BIG");
+    c->tile_big_forced = tb && atoi(tb) != 0;
+    const bool big_buf = !golk::multi_fits(c->nw, c->pitch, c->buf_rows);
+    const bool big_can = cfg->width >= 256 && cfg->width % 64 == 0 && c->multi_words == 1 &&
+                         !(cfg->flags & (GOL_FLAG_FORCE_GENERIC | GOL_FLAG_COUNT_EVERY_TURN));
+    if (c->tile_big_forced && !big_can) {
+        delete c;
+        return GOL_EINVAL;
+    }
+    c->tile_big = (big_buf || c->tile_big_forced) && big_can;
+    if (c->tile_big) c->tile_only = true;                 // (K1t alone, searched: K1s / K1w stay out)
     if (c->tile_only) s.multi_variant = golk::kMultiTile;
     if (const char *v = getenv("GOL_MULTI_VARIANT")) {    // A/B experiments only
         const int k = atoi(v);
@@ -436,6 +464,13 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         }
         s.multi_variant = k;
         if (k != golk::kMultiTile) c->tile_only = false;   // (no other kernel runs these widths)
+        if (k != golk::kMultiTile && c->tile_big) {        // (... nor such a buffer)
+            if (c->tile_big_forced) {
+                delete c;
+                return GOL_EINVAL;
+            }
+            c->tile_big = false;
+        }
     }
     const bool blockable = c->fast || c->tile_only;
     const int lane_dw = golk::multi_lane_dwords(c->multi_words, s.multi_variant);
@@ -445,7 +480,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
                                       : (wg ? 16 : (auto_bm >= 48 ? 8 : 6));
     if (const char *v = getenv("GOL_TURNS_PER_LAUNCH")) s.tpl = atoi(v);
     s.tpl = std::max(1, std::min(s.tpl, golk::multi_max_turns(s.multi_variant)));
-    if (blockable && s.tpl > 1 && !golk::multi_fits(c->nw, c->pitch, c->buf_rows))
+    if (blockable && s.tpl > 1 && big_buf && !c->tile_big)
         c->blocking_limited = true;   // reported in gol_info.blocking_limited
     if (!blockable || c->blocking_limited) s.tpl = 1;
     c->halo_valid = cfg->halo;
@@ -508,8 +543,13 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         if (int rc2 = initial_tile_shape(c, cntb)) {
             // a tile_only board no tile shape fits (a few rows) and nothing pinned: one turn per
             // launch, as before; every other failure is the caller's shape
-            if (!c->tile_only || pinned || getenv("GOL_TILE") || cfg->band_rows > 0)
+            if (!c->tile_only || pinned || getenv("GOL_TILE") || cfg->band_rows > 0 ||
+                c->tile_big_forced)
                 return bail(rc2);
+            if (c->tile_big) {                   // (2 GiB of a few rows: no window fits)
+                c->tile_big = false;
+                c->blocking_limited = big_buf;
+            }
             LaunchShape one;
             one.multi_variant = golk::kMultiTile;
             set_shape(c, std::move(one));
@@ -525,7 +565,9 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         !(at && atoi(at) == 2) && known_shape(c, &ks)) {
         apply_tile(c, ks.t);
         if (ks.short_K >= 2 && ks.short_K < ks.t.K &&
-            golk::tile_shape_ok(c->nw, ks.short_K, ks.short_th, ks.t.tw, ks.t.seg)) {
+            golk::tile_shape_ok(c->nw, ks.short_K, ks.short_th, ks.t.tw, ks.t.seg) &&
+            (!c->tile_big || golk::tile_big_ok(cfg->width, c->buf_rows, c->pitch, ks.short_K,
+                                               ks.short_th, ks.t.seg))) {
             s.short_k = ks.short_K;
             s.short_band = ks.short_th;
         }
@@ -542,7 +584,8 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
                           (cfg->turns_per_launch <= 0 || cfg->turns_per_launch <= 8);
     const TuneKey key{dev, cfg->width, c->buf_rows, cfg->turns_per_launch,
                       (tune_small ? 4 : 0) | (tune_var ? 2 : 0) | (pinned ? 1 : 0) |
-                          (s.multi_variant << 3) | (cntb ? 1 << 24 : 0)};
+                          (s.multi_variant << 3) | (cntb ? 1 << 24 : 0) |
+                          (c->tile_big ? 1 << 25 : 0)};
     const char *tc = getenv("GOL_AUTOTUNE_CACHE");
     const bool use_cache = !tc || atoi(tc) != 0;
     bool cached = false;

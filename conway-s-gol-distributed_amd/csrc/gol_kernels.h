@@ -34,6 +34,10 @@ struct StepArgs {
     // k_step_wg wave priorities (4-wave workgroups): wave w runs at s_setprio
     // (wg_prio >> 2w) & 3; 0 = the built-in grading
     unsigned wg_prio;
+    // k_step_tile: 1 = the big form (k_step_tile_big: the buffer resources rebased per tile)
+    // whatever the buffer's size -- GOL_TILE_BIG=1; a buffer of 2 GiB or more runs it anyway.
+    // (it sits in what was padding before the pointer below: no other member moves)
+    int tile_big;
     // engine-owned error word (host-mapped pinned memory, or nullptr): a k_step_wg wait that
     // gives up stores a kDevErr* code here, and the engine reports it as GOL_EHIP at its next
     // synchronising call instead of returning a corrupt board with GOL_OK
@@ -287,6 +291,86 @@ constexpr bool tile_seam_codes_shipped()
     return true;
 }
 static_assert(tile_seam_codes_shipped(), "kTileSeamCodes: a subset of kTileCodes, W = 1");
+// the codes k_step_tile_big is instantiated for (gol_tile_big.hip tile_big_kernel): K1t on a
+// buffer of 2 GiB or more, whose rows a 32-bit byte offset from the buffer's start no longer
+// reaches (tile_pass BIG, tile_window below).  One word per lane, plain launches, whole-word
+// rows, no counted form.  The 65536^2 and 16384^2 pins (516, 112), the 6-waves-per-SIMD
+// variant (524), and what the big-board search (gol_tune.cpp) draws from: one in-order code,
+// both loop forms of ORD 1 and ORD 5, one ORD 6.  Each one is pinned by tests/test_gpu_big.py
+// through gol_tile_big_codes.
+constexpr int kTileBigCodes[] = {
+    16,                                                                          // ORD 0
+    108, 112, 116,                                                               // ORD 1
+    512, 516, 524,                                                               // ORD 5
+    616,                                                                         // ORD 6
+};
+constexpr bool tile_code_big(int code)
+{
+    for (int c : kTileBigCodes)
+        if (c == code) return true;
+    return false;
+}
+constexpr bool tile_big_codes_shipped()
+{
+    for (int c : kTileBigCodes)
+        if (!tile_code_shipped(c) || c >= 1000) return false;
+    return true;
+}
+static_assert(tile_big_codes_shipped(), "kTileBigCodes: a subset of kTileCodes, W = 1");
+
+// ---- the big form's window.  A tile at buffer row y0, tile_h rows high, run `turns` turns deep
+// touches only buffer rows (y0 - turns + j) mod modrows, j = 0 .. tile_h + 2 turns - 1.  With
+// modrows >= tile_h + 2 turns that window wraps past the buffer's last row at most once: rows_a
+// rows from row0 on, then rows_b rows from row 0 on (none unless it wraps).  The kernel bases
+// one buffer resource at each part (base_a_bytes past the buffer's start; the second part's is
+// the buffer's start) and keeps 32-bit offsets within the part; every byte quantity here is
+// 64-bit.  false (and empty parts): y0 outside [0, modrows), modrows < tile_h + 2 turns, or a
+// window of 2 GiB or more.
+constexpr int64_t kTileWindowMaxBytes = (int64_t)1 << 31;
+__host__ __device__ inline bool tile_window(int64_t modrows, int64_t pitch_words, int64_t y0, int turns,
+                                            int tile_h, int64_t *row0, int64_t *rows_a,
+                                            int64_t *rows_b, uint64_t *base_a_bytes)
+{
+    *row0 = *rows_a = *rows_b = 0;
+    *base_a_bytes = 0;
+    const int64_t rows = (int64_t)tile_h + 2 * (int64_t)turns;
+    if (turns < 1 || tile_h < 1 || pitch_words < 1 || y0 < 0 || y0 >= modrows || modrows < rows)
+        return false;
+    // (rows first: pitch_words * 8 * rows stays far below 2^63 once rows < 2^31 / 8)
+    if (pitch_words >= kTileWindowMaxBytes / 8 || rows * (pitch_words * 8) >= kTileWindowMaxBytes)
+        return false;
+    const int64_t r0 = y0 - turns < 0 ? y0 - turns + modrows : y0 - turns;
+    const int64_t ra = rows < modrows - r0 ? rows : modrows - r0;
+    *row0 = r0;
+    *rows_a = ra;
+    *rows_b = rows - ra;
+    *base_a_bytes = (uint64_t)r0 * (uint64_t)pitch_words * 8u;
+    return true;
+}
+// the buffer a k_step_tile launch addresses runs the big form: forced, or 2 GiB and more
+inline bool tile_buffer_big(long long modrows, long long pitch_words, bool forced)
+{
+    return forced || modrows * pitch_words * 8 >= (1ll << 31);
+}
+// a shape the big form runs on that buffer: a code of the set (one word per lane), whole-word
+// rows of at least 256 cells, and a window that wraps at most once and stays below 2 GiB
+inline bool tile_big_ok(int width, long long modrows, long long pitch_words, int turns, int tile_h,
+                        int code)
+{
+    int64_t r0, ra, rb;
+    uint64_t ba;
+    return width >= 256 && width % 64 == 0 && tile_code_big(code) &&
+           tile_window(modrows, pitch_words, 0, turns, tile_h, &r0, &ra, &rb, &ba);
+}
+// the tallest tile such a buffer takes at that depth (the repacked narrow column's tiles are
+// taller than the launch's tile height: tile_grid_big below)
+inline int tile_big_max_h(long long modrows, long long pitch_words, int turns)
+{
+    const long long by_bytes = ((1ll << 31) - 1) / (pitch_words * 8) - 2 * turns;
+    const long long by_rows = modrows - 2 * turns;
+    const long long h = by_rows < by_bytes ? by_rows : by_bytes;
+    return h < 0 ? 0 : h > (1 << 30) ? 1 << 30 : (int)h;
+}
 
 // ---- the row seam.  A row of `width` cells, width % 64 = r in 1 .. 63, has nw = L + 1 words;
 // its last word w[L] holds r cells and zero padding (the board invariant).  K1t's lanes hold
@@ -360,6 +444,27 @@ struct TileGrid {
     long long tiles() const { return (long long)ntx_main * nty_main + n_narrow; }
 };
 TileGrid tile_grid(int nw, int rows, int turns, int tile_h, int tile_w, int seg);
+// (gol_tile_big.hip) the k_step_tile_big instantiation of a code, or nullptr
+void *tile_big_kernel(int code);
+// tile_grid for a launch of the big form: the narrow column's tiles no taller than max_h
+// (tile_big_max_h: their window, too, wraps at most once and stays below 2 GiB) -- more of
+// them, or no repack when that saves no workgroup.  A real board of 2 GiB or more has far more
+// rows than any tile; the cap binds on the small buffers the form is forced on.
+inline TileGrid tile_grid_big(int nw, int rows, int turns, int tile_h, int tile_w, int seg, int max_h)
+{
+    TileGrid g = tile_grid(nw, rows, turns, tile_h, tile_w, seg);
+    if (g.n_narrow > 0 && g.narrow_h > max_h) {
+        const long long n = max_h > 0 ? ((long long)rows + max_h - 1) / max_h : g.nty_main;
+        if (n >= g.nty_main) {
+            g.ntx_main += 1;
+            g.n_narrow = g.narrow_w = g.narrow_h = 0;
+        } else {
+            g.n_narrow = (int)n;
+            g.narrow_h = (int)((rows + n - 1) / n);
+        }
+    }
+    return g;
+}
 // workgroups of a plain launch of `turns` turns (tile_grid); turns = 0: the rectangular grid
 // ntx x nty of the resident kernels (K1p / K1q / K1r find their neighbours by tile index)
 long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg, int turns = 0);

@@ -31,6 +31,7 @@ golk::StepArgs whole_buffer_args(const gol_ctx *c)
     a.variant = c->variant;
     a.multi_words = c->multi_words;
     a.wg_prio = c->wg_prio;
+    a.tile_big = c->tile_big_forced ? 1 : 0;
     a.err = c->d_err;
     return a;
 }
@@ -149,7 +150,11 @@ Launch plan_launch(gol_ctx *c, int64_t room)
     const int64_t nl = (room + s.tpl - 1) / s.tpl;
     const int k = (int)((room + nl - 1) / nl);
     if (!golk::multi_ok(c->cfg.width, k, s.multi_variant, s.tile_seg)) return L;
-    return Launch{k, s.multi_variant, band_for_depth(c, k), s.tile_w, s.tile_seg};
+    const int band = band_for_depth(c, k);
+    // (a big engine: no depth at which the tile's window would not fit -- one turn instead)
+    if (c->tile_big && !golk::tile_big_ok(c->cfg.width, c->buf_rows, c->pitch, k, band, s.tile_seg))
+        return L;
+    return Launch{k, s.multi_variant, band, s.tile_w, s.tile_seg};
 }
 
 const std::vector<Launch> *timed_sequence(const gol_ctx *c, int64_t turns)
@@ -397,6 +402,21 @@ int gol_tile_count_codes(int32_t *codes, int32_t cap)
 int gol_tile_seam_codes(int32_t *codes, int32_t cap)
 {
     return code_list(golk::kTileSeamCodes, (int)std::size(golk::kTileSeamCodes), codes, cap);
+}
+
+int gol_tile_big_codes(int32_t *codes, int32_t cap)
+{
+    return code_list(golk::kTileBigCodes, (int)std::size(golk::kTileBigCodes), codes, cap);
+}
+
+int gol_tile_window(int64_t modrows, int64_t pitch_words, int64_t y0, int32_t turns, int32_t tile_h,
+                    int64_t *row0, int64_t *rows_a, int64_t *rows_b, uint64_t *base_a_bytes)
+{
+    if (!row0 || !rows_a || !rows_b || !base_a_bytes) return GOL_EINVAL;
+    return golk::tile_window(modrows, pitch_words, y0, turns, tile_h, row0, rows_a, rows_b,
+                             base_a_bytes)
+               ? GOL_OK
+               : GOL_EINVAL;
 }
 
 // (the product library has no K1p / K1q kernels: empty lists)

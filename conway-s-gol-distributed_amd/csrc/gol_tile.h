@@ -228,8 +228,13 @@ struct RingArgs {
 // the first tile column and the ones that reach column L) and the store stage (the lane of
 // column L clears its bits r .. 63: the padding of both boards stays zero) differ; the turns
 // and the LDS exchange are the plain kernel's.  One word per lane, plain launches, no counts.
+// BIG (k_step_tile_big: a buffer of 2 GiB or more, whose rows a 32-bit byte offset from its start
+// does not reach): the buffer resources are rebased per workgroup onto the rows the tile touches
+// (gol_kernels.h, tile_window) -- a 64-bit base formed on the scalar unit, 32-bit offsets within
+// the window, num_records the window's bytes.  Again only the load and the store stage differ
+// (below); one word per lane, plain launches, whole-word rows, no counts.
 template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false,
-          bool SEAM = false>
+          bool SEAM = false, bool BIG = false>
 __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                                           uint64_t *__restrict__ out, const StepArgs &a,
                                           int turns, const TilePos &pos,
@@ -315,8 +320,39 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     const uint32_t lstep = rev ? span - pitch_b : pitch_b;   // (a reversed segment loads upwards)
     const __amdgpu_buffer_rsrc_t rin =
         __builtin_amdgcn_make_buffer_rsrc((void *)in, (short)0, (int)span, kBufFlags);
+    static_assert(!BIG || (W == 1 && !PERSIST && !RING && !CNT && !SEAM && ORD != 3 && ORD < 7),
+                  "big launches: plain k_step_tile, one word per lane, no seam, no counts");
+    // BIG: the window's two parts (rows [0, big_ra) of the tile from buffer row row0 on, rows
+    // [big_ra, big_ra + big_rb) from buffer row 0 on: none unless the tile wraps the torus) and
+    // the stored rows [y0, y0 + big_rs), each behind a resource of its own whose range is that
+    // part alone -- an offset outside it is dropped by the range check, whatever lies there.
+    // All of it wave-uniform (the tile's position and the launch's arguments).
+    [[maybe_unused]] int big_ra = 0, big_rb = 0, big_rs = 0;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rin_a = rin, rin_b = rin;
+    [[maybe_unused]] auto big_rsrc = [](const void *p, uint64_t byte, int rows, uint32_t row_b) {
+        const uint64_t ad = (uint64_t)(uintptr_t)p + byte;
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ad);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ad >> 32));
+        const int bytes = __builtin_amdgcn_readfirstlane((int)((uint32_t)rows * row_b));
+        return __builtin_amdgcn_make_buffer_rsrc((void *)(uintptr_t)(((uint64_t)hi << 32) | lo),
+                                                 (short)0, bytes, kBufFlags);
+    };
+    if constexpr (BIG) {
+        int64_t w0, wa, wb;
+        uint64_t ba;
+        // (host-checked, launch_tile: the window wraps at most once and is below 2 GiB; a tile
+        // for which that fails gets empty parts -- it loads zeros and stores nothing)
+        (void)tile_window(M, a.pitch, y0, K, TH, &w0, &wa, &wb, &ba);
+        big_ra = __builtin_amdgcn_readfirstlane((int)wa);
+        big_rb = __builtin_amdgcn_readfirstlane((int)wb);
+        big_rs = big_ra > 0 ? max(0, min(TH, a.row_hi - y0)) : 0;
+        rin_a = big_rsrc(in, ba, big_ra, pitch_b);
+        rin_b = big_rsrc(in, 0, big_rb, pitch_b);
+    }
+    // (BIG: rows [y0, y0 + TH) below row_hi never wrap; the store offsets count from row y0)
     const __amdgpu_buffer_rsrc_t rout =
-        __builtin_amdgcn_make_buffer_rsrc((void *)out, (short)0, (int)span, kBufFlags);
+        BIG ? big_rsrc(out, (uint64_t)(uint32_t)y0 * pitch_b, big_rs, pitch_b)
+            : __builtin_amdgcn_make_buffer_rsrc((void *)out, (short)0, (int)span, kBufFlags);
 
     // PERSIST: loads bypass this CU's vector L1 (sc1): block b reads rows other CUs wrote
     // since block b - 2 left lines of the same buffer in it, and the L1 is never refreshed
@@ -340,7 +376,69 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     // nearly every wave): one lane offset, the rows stepped by the scalar offset of the buffer
     // instruction -- no VALU per row.  Otherwise the offset wraps row by row.
     // (SEAM: the seam tiles load in their own way, below)
-    if (SEAM && seam_tile) {
+    // BIG: three forms, picked on the scalar unit.  Every row of the wave in the window's first
+    // part (nearly every wave): one lane offset from the part's base, the rows stepped by the
+    // instruction's scalar offset -- all of it inside the part by the ballot, so nothing relies
+    // on the range check, which sees the lane offset without the scalar part.  Otherwise the
+    // offset is formed per row in the lane's register, where the range check does see it, with
+    // the scalar offset 0: a tile that does not wrap loads through the one resource (its rows
+    // past the window -- the last segments' surplus -- are clamped to the window's end, out of
+    // range: zeros, which no stored cell's cone reaches); a tile that wraps (the first and
+    // last tile rows of a torus) loads every row through both resources and selects per lane
+    // -- a row's offset is in range in exactly one part: below the first part's end in the
+    // one, negative (above 2^31 as unsigned) or past the end in the other.  kBigChunk rows at a
+    // time, as the seam stage: no more than that many row pairs are held beside the segment.
+    if constexpr (BIG) {
+        const int tr0 = (live ? seg : 0) * SEG;          // the lane's first tile row
+        const uint32_t cb = (uint32_t)gx * 8u;
+        const int wlim = big_ra + big_rb;
+        if (__builtin_amdgcn_ballot_w64(tr0 + SEG > big_ra) == 0) {
+            const uint32_t o = (uint32_t)tr0 * pitch_b + cb;
+#pragma unroll
+            for (int i = 0; i < SEG; ++i) {
+                const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rin_a, o, (uint32_t)i * pitch_b, kLoadAux);
+                v[i][0] = w.x;
+                v[i][1] = w.y;
+            }
+        } else if (big_rb == 0) {
+#pragma unroll
+            for (int i = 0; i < SEG; ++i) {
+                const uint32_t o = (uint32_t)min(tr0 + i, wlim) * pitch_b + cb;
+                const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rin_a, o, 0, kLoadAux);
+                v[i][0] = w.x;
+                v[i][1] = w.y;
+            }
+        } else {
+            constexpr int kBigChunk = 4;
+            int tb = tr0;
+#pragma unroll
+            for (int c0 = 0; c0 < SEG; c0 += kBigChunk) {
+                u32x2 pa[kBigChunk], pb[kBigChunk];
+#pragma unroll
+                for (int j = 0; j < kBigChunk; ++j) {
+                    if (c0 + j < SEG) {
+                        const int t = min(tb + c0 + j, wlim);
+                        const uint32_t oa = (uint32_t)t * pitch_b + cb;
+                        const uint32_t ob = (uint32_t)(t - big_ra) * pitch_b + cb;
+                        pa[j] = __builtin_amdgcn_raw_buffer_load_b64(rin_a, oa, 0, kLoadAux);
+                        pb[j] = __builtin_amdgcn_raw_buffer_load_b64(rin_b, ob, 0, kLoadAux);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < kBigChunk; ++j) {
+                    if (c0 + j < SEG) {
+                        const bool second = tb + c0 + j >= big_ra;
+                        v[c0 + j][0] = second ? pb[j].x : pa[j].x;
+                        v[c0 + j][1] = second ? pb[j].y : pa[j].y;
+                    }
+                }
+                // (the next chunk's loads wait for this chunk's words, as in the seam stage)
+                if (c0 + kBigChunk < SEG)
+                    asm volatile("" : "+v"(tb) : "v"(v[c0 + kBigChunk - 1][0]),
+                                 "v"(v[c0 + kBigChunk - 1][1]));
+            }
+        }
+    } else if (SEAM && seam_tile) {
     } else if (!kHalo && __builtin_amdgcn_ballot_w64(r + SEG > M) == 0) {
 #pragma unroll
         for (int i = 0; i < SEG; ++i) load_row(i, off, (uint32_t)i * pitch_b);
@@ -1055,7 +1153,13 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         const int t0 = (wave * G + sg) * SEG;
         const int top = min(K + TH, a.row_hi - (y0 - K));    // (wave-uniform)
         const int lo = min(max(K - t0, 0), SEG), hi = min(max(top - t0, 0), SEG);
-        uint32_t so = (uint32_t)(y0 - K + t0) * pitch_b + (uint32_t)(x0 + sc - 1) * (8u * W);
+        // BIG: rout starts at row y0, so the lane's first row is t0 - K rows from it.  A lane
+        // whose segment starts above the stored rows (t0 < K, also where y0 - K < 0) holds that
+        // negative count times the pitch modulo 2^32; it steps by one pitch per row in the
+        // lane's register and is exact from the first stored row on: (t0 + i - K) pitch + the
+        // column, below the stored rows' bytes and so below 2^31.  A lane that stores its whole
+        // segment under the scalar step has t0 >= K: its offset is a stored row's, in range.
+        uint32_t so = (uint32_t)(BIG ? t0 - K : y0 - K + t0) * pitch_b + (uint32_t)(x0 + sc - 1) * (8u * W);
         // SEAM: the tile that holds column L (wave-uniform) clears that lane's bits r .. 63 --
         // the wrapped cells it carried through the turns -- so the padding stays zero
         if constexpr (SEAM) {
@@ -1349,6 +1453,20 @@ __global__ __launch_bounds__(1024, (SEG <= 16 ? 8 : 6)) void k_step_tile_seam(co
     const int tile = tile_of_block(L.ntiles);
     if (tile >= L.ntiles) return;                        // the whole workgroup
     tile_pass<SEG, ORD, 1, false, false, false, true>(in, out, a, turns, tile_pos(a, L, tile));
+}
+
+// k_step_tile on a buffer of 2 GiB or more (tile_pass BIG; the instantiations:
+// golk::kTileBigCodes, gol_tile_big.hip).  Its own entry point: the other kernels stay as they
+// are.  The waves per SIMD of the plain kernel of the same code are asked for, as for the seam
+// form (8 up to SEG 16, 6 at SEG 24: DESIGN.md "K1t on boards of 2 GiB and more" has both tables;
+// no big kernel spills).
+template <int SEG, int ORD>
+__global__ __launch_bounds__(1024, (SEG <= 16 ? 8 : 6)) void k_step_tile_big(
+    const uint64_t *__restrict__ in, uint64_t *__restrict__ out, StepArgs a, int turns, TileLaunch L)
+{
+    const int tile = tile_of_block(L.ntiles);
+    if (tile >= L.ntiles) return;                        // the whole workgroup
+    tile_pass<SEG, ORD, 1, false, false, false, false, true>(in, out, a, turns, tile_pos(a, L, tile));
 }
 
 // k_step_tile with the per-turn alive counts fused (tile_pass CNT; the instantiations:

@@ -316,8 +316,18 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
 {
     const int rows = a.row_hi - a.row_lo;
     if (!tile_shape_ok(a.nw, turns, a.band, a.tile_w, a.tile_seg, a.width)) return hipErrorInvalidValue;
+    // a buffer of 2 GiB or more (or GOL_TILE_BIG=1: StepArgs::tile_big): the big form, on the
+    // shapes it runs -- never the plain kernel, whose 32-bit offsets do not reach such a buffer's
+    // rows.  Every tile's window wraps at most once and stays below 2 GiB: the launch's tile
+    // height by tile_big_ok, the repacked narrow column's by tile_grid_big.
+    const bool big = tile_buffer_big(a.modrows, a.pitch, a.tile_big != 0);
+    if (big && (a.counts || !tile_big_kernel(a.tile_seg) ||
+                !tile_big_ok(a.width, a.modrows, a.pitch, turns, a.band, a.tile_seg)))
+        return hipErrorInvalidValue;
     // (ORD 3 with GOL_TILE_PAIR pairs tiles by index: tile_grid leaves its grid rectangular)
-    const TileGrid g = tile_grid(a.nw, rows, turns, a.band, a.tile_w, a.tile_seg);
+    const TileGrid g = big ? tile_grid_big(a.nw, rows, turns, a.band, a.tile_w, a.tile_seg,
+                                           tile_big_max_h(a.modrows, a.pitch, turns))
+                           : tile_grid(a.nw, rows, turns, a.band, a.tile_w, a.tile_seg);
     const int ntx = g.ntx_main;
     const long long ntiles = g.tiles();
     if (ntiles <= 0 || ntiles > (1 << 24)) return hipErrorInvalidValue;
@@ -341,7 +351,8 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
     // kernel with the counts dropped)
     // a width that is no multiple of 64: the seam kernel (which has no counted form)
     const bool seam = a.width % 64 != 0;
-    void *fn = seam ? (a.counts ? nullptr : tile_seam_kernel(a.tile_seg))
+    void *fn = big    ? tile_big_kernel(a.tile_seg)
+               : seam ? (a.counts ? nullptr : tile_seam_kernel(a.tile_seg))
                : a.counts ? tile_cnt_kernel(a.tile_seg)
                           : tile_kernel(a.tile_seg);
     if (!fn || (a.counts && !tile_code_counted(a.tile_seg))) return hipErrorInvalidValue;

@@ -100,7 +100,8 @@ double tile_model_us(int ncu, int nw, int rows, int K, int th, int tw, int seg, 
 // the tallest tile the workgroup holds (16 waves) and the heights whose tile count fills 1..4
 // resident tiles per CU or a few more tile rows.
 // cnt: for a count engine's fused launches -- codes with a counted instantiation only.
-std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt, int width)
+std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool cnt, int width,
+                                       bool big)
 {
     // SEG, and SEG + 100 for the interior-rows-first turn order (gol_tile.hip)
     static constexpr int kSegs[] = {2, 3, 4, 6, 8, 12, 16, 24, 32, 40, 48,
@@ -119,7 +120,7 @@ std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool
             const long long ntx = (nw + tw - 1) / tw;
             for (int seg : kSegs) {
                 if (cnt && !golk::tile_code_counted(seg)) continue;
-                if (!seam_pickable(width, seg)) continue;
+                if (!seam_pickable(width, seg) || (big && !golk::tile_code_big(seg))) continue;
                 const int thmax = golk::kTileMaxWavesHost * G * (seg % 100) - 2 * K;
                 if (thmax < 1) continue;
                 std::vector<long long> ntys;
@@ -129,6 +130,7 @@ std::vector<TileShape> tile_candidates(int ncu, int nw, int rows, int keep, bool
                     ntys.push_back(std::max(nty0, ((long long)ncu * per_cu + ntx - 1) / ntx));
                 for (long long nty : ntys) {
                     const int th = (int)std::max<long long>(1, (rows + nty - 1) / nty);
+                    if (big && !golk::tile_big_ok(width, rows, nw, K, th, seg)) continue;
                     const double m = tile_model_us(ncu, nw, rows, K, th, tw, seg, width);
                     if (m > 0 && (best.K == 0 || m < best.model_us)) best = {K, th, tw, seg, m};
                 }
@@ -225,6 +227,8 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
         int th = p.wv * G * (p.seg % 100) - 2 * p.K;
         if (p.th > 0) th = std::min(th, p.th);
         th = std::min(th, rows);
+        // (a big engine: the codes of golk::kTileBigCodes, windows the form takes)
+        if (c->tile_big && !golk::tile_big_ok(width, rows, c->pitch, p.K, th, p.seg)) return TileShape{};
         if (th < std::min(8, rows) || (cnt && !golk::tile_code_counted(p.seg)) ||
             !seam_pickable(width, p.seg) || !golk::tile_shape_ok(nw, p.K, th, p.tw, p.seg, width))
             return TileShape{};
@@ -272,6 +276,10 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
         return best;
     };
     P cur{kfix > 0 ? kfix : 32, 8, tws.empty() ? 30 : tws[0], W == 1 ? (cnt ? 516 : 16) : 1008};
+    // a big engine starts from the 65536^2 pin: 30 lanes x 452 rows of ORD 5 SEG 16 in 16-wave
+    // workgroups at K = 30 (the K = 20 pin, 30 x 472, is timed beside it below)
+    const bool big_seed = c->tile_big && W == 1 && shape(P{kfix > 0 ? kfix : 30, 16, 30, 516}).K;
+    if (big_seed) cur = P{kfix > 0 ? kfix : 30, 16, 30, 516};
     // clock ramp, and the repetitions that make a measurement ~0.5 ms of launches
     {
         TileShape t0 = shape(cur);
@@ -296,6 +304,7 @@ TileShape tile_search(gol_ctx *c, int kfix, float *us, int W)
             cur = p;
         }
     };
+    if (big_seed && kfix <= 0) improve(P{20, 16, 30, 516});
     if ((long long)nw * rows < (1ll << 23)) {
         // boards up to 16384^2: SEG x width x waves jointly first (one turn order) -- one
         // parameter at a time settled on 5120^2 at 18-word tiles of SEG 8 (0.76 us per turn)

@@ -132,6 +132,10 @@ SIGNATURES = {
     "gol_tile_grid": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(ctypes.c_int32)]),
     "gol_tile_count_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_seam_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "gol_tile_big_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    "gol_tile_window": (_i32, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _i32, _i32,
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]),
     "gol_seam_word": (_i32, [ctypes.POINTER(ctypes.c_uint64), _i32, _i32, _i32,
                              ctypes.POINTER(ctypes.c_uint64)]),
     "gol_tile_persist_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),

@@ -96,7 +96,10 @@ typedef struct gol_config {
                                   Widths of at least 256 cells block: multiples of 128 on
                                   every multi-turn kernel, the others on k_step_tile alone
                                   (gol_tile_seam_codes where width % 64 != 0); narrower
-                                  boards run one turn per launch                        */
+                                  boards run one turn per launch.  A board buffer of 2 GiB
+                                  or more blocks on k_step_tile alone (gol_tile_big_codes),
+                                  and only with width % 64 == 0 and no per-turn counts
+                                  (gol_info.blocking_limited)                            */
 } gol_config;
 
 typedef struct gol_info {
@@ -115,8 +118,13 @@ typedef struct gol_info {
     int64_t  nonbinary_cells;   /* cells that were neither 0 nor 255 at load           */
     int64_t  launches;          /* stencil kernel launches since load                  */
     int32_t  blocking_limited;  /* 1 = temporal blocking is off because a board buffer is
-                                   >= 2 GiB (the multi-turn kernel's 32-bit buffer offsets):
-                                   every launch runs one turn                          */
+                                   >= 2 GiB and the engine is one that k_step_tile's big form
+                                   (buffer resources rebased per tile: gol_tile_big_codes)
+                                   does not run -- a count engine, a width that is no
+                                   multiple of 64 or below 256, a forced-generic engine:
+                                   every launch runs one turn.  Every other engine of that
+                                   size blocks, on tiles whose rows (tile height + 2 x
+                                   depth) span less than 2 GiB                          */
     int32_t  shape_source;      /* where the multi-turn launch shape came from: 0 = defaults
                                    or the caller (gol_config / GOL_* experiments), 1 = the
                                    create-time timing search, 2 = the pinned table of
@@ -228,6 +236,23 @@ int gol_tile_count_codes(int32_t *codes, int32_t cap);
  * row seam: the torus wraps in x inside the row's last word): the codes such an engine runs
  * multi-turn launches on; same convention. */
 int gol_tile_seam_codes(int32_t *codes, int32_t cap);
+/* The subset with a form for board buffers of 2 GiB and more (k_step_tile_big: every tile
+ * addresses its own window of rows through 64-bit bases, so no byte offset depends on the
+ * buffer's size): the codes such an engine runs multi-turn launches on, width % 64 == 0 and no
+ * per-turn counts; same convention.  GOL_TILE_BIG=1 in the environment at create forces the form
+ * on a buffer of any size (tests, A/B runs); the create then fails with GOL_EINVAL for an
+ * engine or shape the form does not run. */
+int gol_tile_big_codes(int32_t *codes, int32_t cap);
+/* The rows such a tile touches: a tile at buffer row y0 (0 <= y0 < modrows) of tile_h rows, run
+ * `turns` turns deep on a buffer of modrows rows of pitch_words words, reads rows
+ * (y0 - turns + j) mod modrows, j = 0 .. tile_h + 2 turns - 1: *rows_a rows from row *row0 on,
+ * then *rows_b rows from row 0 on (0 unless the window wraps past the last row).
+ * *base_a_bytes = *row0 x pitch_words x 8, the first part's byte distance from the buffer's
+ * start (64-bit).  Needs no device.  GOL_EINVAL for a window of 2 GiB or more, for
+ * modrows < tile_h + 2 turns (a window that would wrap twice) and for arguments out of range. */
+int gol_tile_window(int64_t modrows, int64_t pitch_words, int64_t y0, int32_t turns,
+                    int32_t tile_h, int64_t *row0, int64_t *rows_a, int64_t *rows_b,
+                    uint64_t *base_a_bytes);
 /* The word a k_step_tile lane holds at virtual lane column v of a row of `width` cells: cells
  * 64 v .. 64 v + 63 (mod width), bit b = cell 64 v + b.  row: the row's ceil(width / 64) words
  * (padding bits zero) in `layout` (0 standard, 1 interleaved: even cells in the low dword, odd
