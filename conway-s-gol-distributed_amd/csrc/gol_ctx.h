@@ -8,7 +8,7 @@
 //                    report plans and tables; no stream or event call
 //   gol_step.cpp     gol_step / gol_step_overlap: launches, stream and event ordering, the chunk
 //                    pipeline, the read-job queue, the control word
-//   gol_io.cpp       load, read-out, counts, alive and flip lists
+//   gol_io.cpp       load, read-out, counts, alive and flip lists, windows (gol_window.h)
 //   gol_halo.cpp     halo exchange
 //   gol_blocks.cpp   K1p / K1q / K1r host side and the k_step_wg wait diagnostic (tools build;
 //                    stubs in the product)

@@ -1,8 +1,9 @@
-// gol_io.cpp — load, read-out, counts, alive and flip lists.
+// gol_io.cpp — load, read-out, counts, alive and flip lists, windows.
 #include <algorithm>
 #include <cstring>
 
 #include "gol_ctx.h"
+#include "gol_window.h"
 
 using namespace goleng;
 
@@ -69,6 +70,22 @@ extern "C" int read_board_bytes(gol_ctx *c, uint8_t *out)
     }
     return GOL_OK;
 }
+
+// ---- windows (gol_window.h).  The arguments of a window call: in range, and on a strip engine
+// (read calls: owned = true) every window row an owned row.
+bool window_ok(const gol_ctx *c, int32_t x, int32_t y, int32_t w, int32_t h, bool owned)
+{
+    if (x < 0 || x >= c->cfg.width || y < 0 || y >= c->cfg.height || w < 1 || w > c->cfg.width ||
+        h < 1 || h > c->cfg.height)
+        return false;
+    if (owned && is_strip(c) &&
+        (y < c->cfg.row_offset || (long long)y + h > (long long)c->cfg.row_offset + c->cfg.rows))
+        return false;
+    return true;
+}
+// the buffer row of window row 0 of a read call, and the row count its rows wrap at (a torus
+// engine's buffer is the board; a strip's window never reaches its buffer's end)
+int window_brow0(const gol_ctx *c, int32_t y) { return y - c->cfg.row_offset + own_lo(c); }
 
 }  // namespace
 
@@ -404,6 +421,157 @@ int gol_flipped_cells(gol_ctx *c, int64_t *xy, int64_t cap, int64_t *n)
         }
         return GOL_OK;
     });
+}
+
+// ---------------------------------------------------------------- windows
+int gol_read_window(gol_ctx *c, int32_t x, int32_t y, int32_t w, int32_t h, uint8_t *out,
+                    int64_t *turn)
+{
+    if (!c || !out) return GOL_EINVAL;
+    return run_read(c, [&]() -> int {
+        if (!window_ok(c, x, y, w, h, true)) return GOL_EINVAL;
+        if (turn) *turn = c->turn;
+        if (!c->raw_turn0.empty()) {         // the loaded bytes as they are (gol_read_board)
+            const int W = c->cfg.width, rows = c->cfg.rows;
+            for (int j = 0; j < h; ++j) {
+                const uint8_t *src =
+                    c->raw_turn0.data() + (size_t)((y - c->cfg.row_offset + j) % rows) * W;
+                uint8_t *dst = out + (size_t)j * w;
+                const int n = std::min(w, W - x);
+                std::memcpy(dst, src + x, (size_t)n);
+                if (n < w) std::memcpy(dst + n, src, (size_t)(w - n));
+            }
+            return GOL_OK;
+        }
+        DeviceGuard g(c->device);
+        const size_t row_bytes = (size_t)w;
+        const int chunk_rows =
+            (int)std::max<size_t>(1, std::min<size_t>(kStagingBytes / row_bytes, (size_t)h));
+        if (int rc = ensure_staging(c, (size_t)chunk_rows * row_bytes)) return rc;
+        for (int r0 = 0; r0 < h; r0 += chunk_rows) {
+            const int nr = std::min(chunk_rows, h - r0);
+            HIP_OR_FAIL(c, golk::launch_window_unpack(c->board[c->cur], c->cfg.width, c->pitch,
+                                                      c->il, c->buf_rows, window_brow0(c, y), x, w,
+                                                      r0, nr, c->staging, c->stream));
+            HIP_OR_FAIL(c, hipMemcpyAsync(out + (size_t)r0 * row_bytes, c->staging,
+                                          (size_t)nr * row_bytes, hipMemcpyDeviceToHost, c->stream));
+            if (int rc = sync_checked(c)) return rc;
+        }
+        return GOL_OK;
+    });
+}
+
+int gol_window_density(gol_ctx *c, int32_t x, int32_t y, int32_t w, int32_t h, int32_t block,
+                       uint32_t *out, int64_t *turn)
+{
+    if (!c || !out || block < 1 || block > 4096) return GOL_EINVAL;
+    return run_read(c, [&]() -> int {
+        if (!window_ok(c, x, y, w, h, true)) return GOL_EINVAL;
+        if (turn) *turn = c->turn;
+        DeviceGuard g(c->device);
+        // whole block rows per staging chunk (one, however long, when a single one exceeds it)
+        const int nbx = (w + block - 1) / block, nby = (h + block - 1) / block;
+        const size_t brow_bytes = (size_t)nbx * sizeof(uint32_t);
+        const int chunk_brows =
+            (int)std::max<size_t>(1, std::min<size_t>(kStagingBytes / brow_bytes, (size_t)nby));
+        if (int rc = ensure_staging(c, std::max<size_t>((size_t)chunk_brows * brow_bytes, 16)))
+            return rc;
+        for (int J0 = 0; J0 < nby; J0 += chunk_brows) {
+            const int nJ = std::min(chunk_brows, nby - J0);
+            const int r0 = J0 * block;                   // (< h <= 2^31 - 1)
+            const int nr = (int)std::min<long long>((long long)nJ * block, (long long)h - r0);
+            HIP_OR_FAIL(c, hipMemsetAsync(c->staging, 0, (size_t)nJ * brow_bytes, c->stream));
+            HIP_OR_FAIL(c, golk::launch_window_density(c->board[c->cur], c->cfg.width, c->pitch,
+                                                       c->il, c->buf_rows, window_brow0(c, y), x, w,
+                                                       r0, nr, block, (uint32_t *)c->staging,
+                                                       c->stream));
+            HIP_OR_FAIL(c, hipMemcpyAsync(out + (size_t)J0 * nbx, c->staging, (size_t)nJ * brow_bytes,
+                                          hipMemcpyDeviceToHost, c->stream));
+            if (int rc = sync_checked(c)) return rc;
+        }
+        return GOL_OK;
+    });
+}
+
+int gol_write_window(gol_ctx *c, int32_t x, int32_t y, int32_t w, int32_t h, const uint8_t *bytes)
+{
+    if (!c || !bytes) return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    if (!window_ok(c, x, y, w, h, false)) return GOL_EINVAL;
+    if (!c->raw_turn0.empty() || c->blocked_pending)
+        return fail(c, GOL_ESTATE, "gol_write_window: the engine holds a non-binary turn-0 board "
+                                   "(a window has no non-binary semantics)");
+    DeviceGuard g(c->device);
+    const size_t row_bytes = (size_t)w;
+    const int chunk_rows =
+        (int)std::max<size_t>(1, std::min<size_t>(kStagingBytes / row_bytes, (size_t)h));
+    if (int rc = ensure_staging(c, (size_t)chunk_rows * row_bytes)) return rc;
+    c->prev_valid = false;
+    // Buffer row b holds global row (g0 + b) mod height; it lies in the window when
+    // (g0 + b - y) mod height < h, i.e. b = s + t + m x height with s = (y - g0) mod height and t
+    // the window row: one run of h buffer rows per m, cut to the buffer.  A torus engine's runs
+    // are the window's rows up to the board's end (m = 0) and past the wrap (m = -1); a strip's
+    // buffer may hold a global row twice (rows == height with halos), then both copies are
+    // written; it may hold none of the window's, and nothing is.
+    const long long H = c->cfg.height;
+    const long long g0 = (long long)c->cfg.row_offset - c->cfg.halo;
+    const long long s = (((long long)y - g0) % H + H) % H;
+    for (int r0 = 0; r0 < h; r0 += chunk_rows) {
+        const int nr = std::min(chunk_rows, h - r0);
+        bool staged = false;
+        for (long long first = s - H; first < c->buf_rows; first += H) {
+            // window rows [r0, r0 + nr) of this run are buffer rows first + r0 ...
+            const long long lo = std::max<long long>(0, first + r0);
+            const long long hi = std::min<long long>(c->buf_rows, first + r0 + nr);
+            if (lo >= hi) continue;
+            if (!staged) {
+                HIP_OR_FAIL(c, hipMemcpyAsync(c->staging, bytes + (size_t)r0 * row_bytes,
+                                              (size_t)nr * row_bytes, hipMemcpyHostToDevice,
+                                              c->stream));
+                staged = true;
+            }
+            HIP_OR_FAIL(c, golk::launch_window_pack(
+                               c->board[c->cur], c->cfg.width, c->nw, c->pitch, c->il, (int)lo,
+                               (int)(hi - lo), x, w,
+                               c->staging + (size_t)(lo - first - r0) * row_bytes, c->stream));
+        }
+    }
+    return sync_checked(c);
+}
+
+int gol_clear(gol_ctx *c)
+{
+    if (!c) return GOL_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    release_blocked(c);
+    c->prev_valid = false;
+    HIP_OR_FAIL(c, hipMemsetAsync(c->board[0], 0, (size_t)c->buf_rows * c->pitch * 8, c->stream));
+    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    c->cur = 0;
+    c->il = false;
+    clear_dev_err(c);                        // a new board: earlier hand-off failures are moot
+    c->turn = 0;
+    c->progress.store(0);
+    c->launches = 0;
+    c->nonbinary = 0;
+    c->raw_turn0.clear();
+    c->halo_valid = c->cfg.halo;
+    return GOL_OK;
+}
+
+int gol_board_layout(gol_ctx *c)
+{
+    if (!c) return GOL_EINVAL;
+    return run_read(c, [&]() -> int { return c->il ? 1 : 0; });
+}
+
+int gol_window_word(const uint64_t *row, int32_t width, int32_t col, int32_t layout, uint64_t *out)
+{
+    if (!row || !out || width < 2 || col < 0 || col >= width || (layout != 0 && layout != 1))
+        return GOL_EINVAL;
+    *out = golk::window_word(row, width, col, layout == 1);
+    return GOL_OK;
 }
 
 }  // extern "C"

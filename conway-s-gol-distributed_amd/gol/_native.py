@@ -149,6 +149,14 @@ SIGNATURES = {
     "gol_read_packed": (_i32, [_vp, _u64p]),
     "gol_alive_cells": (_i32, [_vp, _i64p, _i64, _i64p]),
     "gol_flipped_cells": (_i32, [_vp, _i64p, _i64, _i64p]),
+    "gol_read_window": (_i32, [_vp, _i32, _i32, _i32, _i32, _u8p, _i64p]),
+    "gol_window_density": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32,
+                                  ctypes.POINTER(ctypes.c_uint32), _i64p]),
+    "gol_write_window": (_i32, [_vp, _i32, _i32, _i32, _i32, _u8p]),
+    "gol_clear": (_i32, [_vp]),
+    "gol_board_layout": (_i32, [_vp]),
+    "gol_window_word": (_i32, [ctypes.POINTER(ctypes.c_uint64), _i32, _i32, _i32,
+                               ctypes.POINTER(ctypes.c_uint64)]),
     "gol_export_halo": (_i32, [_vp, _vp, _vp, _vp]),
     "gol_import_halo": (_i32, [_vp, _vp, _vp, _vp]),
     "gol_copy_halo_from_upper": (_i32, [_vp, _vp]),

@@ -204,6 +204,47 @@ class Engine:
                                               ctypes.byref(n)))
         return out[: n.value]
 
+    # -- windows: w x h cells from (x, y), global coordinates, wrapping in x and y
+    def read_window(self, x: int, y: int, w: int, h: int):
+        """(bytes (h, w) 0 / 255, turn): that window of read_board(), at the window's cost and
+        without a layout conversion; callable from another thread while step() runs."""
+        out = np.zeros((max(int(h), 1), max(int(w), 1)), dtype=np.uint8)
+        t = ctypes.c_int64()
+        self._c(self._L.gol_read_window(self._h, int(x), int(y), int(w), int(h),
+                                        out.ctypes.data_as(N._u8p), ctypes.byref(t)))
+        return out, int(t.value)
+
+    def window_density(self, x: int, y: int, w: int, h: int, block: int):
+        """(alive counts uint32 (ceil(h / block), ceil(w / block)), turn): the window in blocks
+        of block x block cells, 1 <= block <= 4096."""
+        b = int(block)
+        if not 1 <= b <= 4096:
+            raise N.GolError(N.GOL_EINVAL, "block outside 1 .. 4096")
+        out = np.zeros((max(-(-int(h) // b), 1), max(-(-int(w) // b), 1)), dtype=np.uint32)
+        t = ctypes.c_int64()
+        self._c(self._L.gol_window_density(self._h, int(x), int(y), int(w), int(h), b,
+                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           ctypes.byref(t)))
+        return out, int(t.value)
+
+    def write_window(self, x: int, y: int, cells: np.ndarray):
+        """Set the window at (x, y) from a uint8 (h, w) array: 255 = alive, anything else dead.
+        The turn stays.  Strip engines write every buffer row (owned or halo) in the window."""
+        b = np.ascontiguousarray(cells, dtype=np.uint8)
+        if b.ndim != 2:
+            raise ValueError(f"expected a 2-D array, got shape {b.shape}")
+        h, w = b.shape
+        self._c(self._L.gol_write_window(self._h, int(x), int(y), w, h,
+                                         b.ctypes.data_as(N._u8p)))
+
+    def clear(self):
+        """Every cell dead, turn 0 (what load_packed of an empty board leaves)."""
+        self._c(self._L.gol_clear(self._h))
+
+    def board_layout(self) -> int:
+        """0 standard, 1 interleaved: the layout the device board is in now."""
+        return self._c(self._L.gol_board_layout(self._h))
+
     # -- strip halo exchange (device pointers)
     def export_halo(self, top_ptr: int, bottom_ptr: int, stream_ptr: int | None = None):
         self._c(self._L.gol_export_halo(self._h, ctypes.c_void_p(top_ptr),

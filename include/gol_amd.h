@@ -31,7 +31,8 @@
  *
  * Threading: one thread drives an engine (gol_step, loads, halo calls).  The read-only
  * calls (gol_snapshot, gol_get_info, gol_read_board, gol_get_world, gol_read_packed,
- * gol_alive_cells, gol_flipped_cells, gol_turn_counts) may come from other threads at any time: during a gol_step the stepping
+ * gol_alive_cells, gol_flipped_cells, gol_turn_counts, gol_read_window, gol_window_density,
+ * gol_board_layout) may come from other threads at any time: during a gol_step the stepping
  * thread serves them at its next launch boundary, on a turn-consistent board; while the
  * step is parked on GOL_CONTROL_PAUSE they run at once (the reference Server's mutex is
  * held only around the per-turn commit: Server/gol/distributor.go:62-75,131-134).  A run
@@ -320,6 +321,59 @@ int gol_alive_cells(gol_ctx *ctx, int64_t *xy, int64_t cap, int64_t *n);
  * and is dead after it, so it is not reported on that turn although its byte changed (the run
  * driver compares that one turn's bytes on the host). */
 int gol_flipped_cells(gol_ctx *ctx, int64_t *xy, int64_t cap, int64_t *n);
+
+/* ---- Windows: read, count and write a rectangle of the board at a cost proportional to the
+ * rectangle (the whole-board calls above need width x height host bytes -- 16 GiB at 131072^2 --
+ * and convert the whole buffer to the standard layout first; these work on the board in
+ * whichever layout it is in and touch no row outside the window).  No reference counterpart: its
+ * view is one pixel per cell (Local/sdl), its boards cross the RPC boundary whole.
+ * A window is w x h cells whose top-left cell is (x, y) in GLOBAL board coordinates:
+ * 0 <= x < width, 0 <= y < height, 1 <= w <= width, 1 <= h <= height.  Column x + i means
+ * (x + i) mod width and row y + j means (y + j) mod height: a window may cross either wrap, and
+ * never covers a cell twice.  Arguments out of range: GOL_EINVAL, the engine untouched.
+ *
+ * gol_read_window: h x w bytes (0 / 255, row stride w), exactly that window of what
+ * gol_read_board returns (at turn 0 of a non-binary load: the loaded bytes as they are); *turn
+ * (may be NULL) is the turn of that board.  A read-only call: from another thread during a
+ * gol_step it is served at a launch boundary.  Strip engine: every window row must be an owned
+ * row (row_offset <= y and y + h <= row_offset + rows), else GOL_EINVAL.  The board's layout
+ * (gol_board_layout) stays as it is. */
+int gol_read_window(gol_ctx *ctx, int32_t x, int32_t y, int32_t w, int32_t h, uint8_t *out,
+                    int64_t *turn);
+/* The window as alive counts per block x block cells, 1 <= block <= 4096 (a thumbnail of a
+ * board too large to show): ceil(h / block) x ceil(w / block) counts, entry (J, I) = the alive
+ * cells (packed bit set, as gol_snapshot counts) in window rows [J block, min(h, (J + 1) block))
+ * x columns [I block, min(w, (I + 1) block)).  Threading and strip rule as gol_read_window. */
+int gol_window_density(gol_ctx *ctx, int32_t x, int32_t y, int32_t w, int32_t h, int32_t block,
+                       uint32_t *out, int64_t *turn);
+/* Set the window's cells from h x w bytes: 255 = alive, any other value = dead (no non-binary
+ * semantics; GOL_ESTATE while the engine holds the turn-0 board of a non-binary gol_load).  A
+ * stepping-thread call, like the loads.  The turn, the launch count and the recorded per-turn
+ * counts stay; the flip list becomes invalid (gol_flipped_cells: GOL_ESTATE until the next
+ * one-turn step); padding bits stay 0.
+ * Strip engine: every BUFFER row, owned or halo, whose global row (row_offset - halo + b) mod
+ * height lies in the window is written -- both copies when the buffer holds a global row twice,
+ * none (GOL_OK) when it holds none of the window's.  So a caller that applies the same call to
+ * every strip of a board at a window boundary (after an exchange, before the next gol_step)
+ * keeps the strips consistent: each strip's halo rows get what their owner's rows get. */
+int gol_write_window(gol_ctx *ctx, int32_t x, int32_t y, int32_t w, int32_t h,
+                     const uint8_t *bytes);
+/* Every buffer row dead.  Resets what gol_load_packed resets: turn 0, standard layout, the
+ * error word, halo_valid. */
+int gol_clear(gol_ctx *ctx);
+/* The layout the current board buffer is in now: 0 standard, 1 interleaved (what a multi-turn
+ * gol_step leaves; the whole-board read-outs convert it back, the window calls do not). */
+int gol_board_layout(gol_ctx *ctx);
+/* The 64 cells at columns col .. col + 63 (mod width) of one row: bit b of *out = cell
+ * (col + b) mod width, in standard order.  row: the row's ceil(width / 64) words in `layout`
+ * (0 standard, 1 interleaved: even cells in the low dword, odd cells in the high one).  This is
+ * the host build of the function the window kernels fetch their cells with.  With
+ * r = width % 64 != 0 the 64 cells can span THREE words (the tail of word L - 1, the r cells of
+ * the last word L, then word 0), and a row narrower than 64 cells wraps more than once.
+ * GOL_EINVAL for null pointers, width < 2, col outside [0, width) or an unknown layout.  Needs no
+ * device. */
+int gol_window_word(const uint64_t *row, int32_t width, int32_t col, int32_t layout,
+                    uint64_t *out);
 
 /* Strip mode halo exchange.  export: copy the first and the last `halo` owned
  * rows (packed, halo x words_per_row uint64 each) to device buffers `top` and
