@@ -33,13 +33,15 @@ __device__ __forceinline__ uint32_t dpp_from_upper_z(uint32_t v)
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x130, 0xf, 0xf, true);
 }
 
+// (maj3, life_rule and the torus words below also build for the host: gol_resident.h's turn
+// runs them in the library's device-free model of k_step_resident)
 template <typename T>
-__device__ __forceinline__ T maj3(T a, T b, T c) { return (a & b) | (c & (a | b)); }
+__host__ __device__ __forceinline__ T maj3(T a, T b, T c) { return (a & b) | (c & (a | b)); }
 
 // next state from three 2-bit row sums (above a, current b, below c) and the
 // centre bits: T = a + b + c over the 3x3 window incl. the centre.
 template <typename T>
-__device__ __forceinline__ T life_rule(T a0, T a1, T b0, T b1, T c0, T c1, T alive)
+__host__ __device__ __forceinline__ T life_rule(T a0, T a1, T b0, T b1, T c0, T c1, T alive)
 {
     const T u0 = a0 ^ b0 ^ c0;          // bit 0 of T
     const T u1 = maj3(a0, b0, c0);      // carry of the low bits (weight 2)
@@ -49,6 +51,20 @@ __device__ __forceinline__ T life_rule(T a0, T a1, T b0, T b1, T c0, T c1, T ali
     const T h1 = (u1 ^ v0) & ~v1;                       // H == 1
     const T h2 = (u1 & v0 & ~v1) | (~(u1 | v0) & v1);   // H == 2
     return (u0 & h1) | (~u0 & alive & h2);              // T == 3  |  (alive & T == 4)
+}
+
+// The west / east neighbour words of word j of a torus row of nw words whose last word holds
+// nb cells (1 .. 64): bit nb - 1 of the last word is the west neighbour of cell 0, bit 0 of
+// word 0 the east neighbour of the row's last cell.
+__host__ __device__ __forceinline__ uint64_t west_word(const uint64_t *row, int j, int nw, int nb)
+{
+    const uint64_t carry = j > 0 ? (row[j - 1] >> 63) : ((row[nw - 1] >> (nb - 1)) & 1ull);
+    return (row[j] << 1) | carry;
+}
+__host__ __device__ __forceinline__ uint64_t east_word(const uint64_t *row, int j, int nw, int nb)
+{
+    if (j < nw - 1) return (row[j] >> 1) | (row[j + 1] << 63);
+    return (row[j] >> 1) | ((row[0] & 1ull) << (nb - 1));
 }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)

@@ -12,6 +12,7 @@
 #include <set>
 
 #include "gol_ctx.h"
+#include "gol_resident.h"
 
 namespace goleng {
 
@@ -472,7 +473,19 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
             c->tile_big = false;
         }
     }
-    const bool blockable = c->fast || c->tile_only;
+    // GOL_FLAG_RESIDENT, a request: a torus board that k_step_resident holds (by its shape:
+    // golk::resident_plan) runs up to kResidentMaxTurns turns per launch in one workgroup --
+    // nothing is searched, timed or pinned for it.  A depth of 1 (the caller's, or
+    // GOL_TURNS_PER_LAUNCH's) switches it off like any blocking; so do a strip, a forced-generic
+    // engine and a board outside the limits, which all run as without the flag.
+    golk::ResidentPlan rplan;
+    int rtpl = cfg->turns_per_launch > 0 ? cfg->turns_per_launch : golk::kResidentMaxTurns;
+    if (const char *v = getenv("GOL_TURNS_PER_LAUNCH")) rtpl = atoi(v);
+    const bool resident = (cfg->flags & GOL_FLAG_RESIDENT) && cfg->halo == 0 &&
+                          !(cfg->flags & GOL_FLAG_FORCE_GENERIC) && rtpl != 1 &&
+                          golk::resident_plan(cfg->width, cfg->height, &rplan);
+    if (resident) s.multi_variant = golk::kMultiResident;
+    const bool blockable = c->fast || c->tile_only || resident;
     const int lane_dw = golk::multi_lane_dwords(c->multi_words, s.multi_variant);
     const int auto_bm = golk::auto_band_multi(cfg->width, cfg->rows, lane_dw);
     const bool wg = golk::is_wg_variant(s.multi_variant);
@@ -480,6 +493,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
                                       : (wg ? 16 : (auto_bm >= 48 ? 8 : 6));
     if (const char *v = getenv("GOL_TURNS_PER_LAUNCH")) s.tpl = atoi(v);
     s.tpl = std::max(1, std::min(s.tpl, golk::multi_max_turns(s.multi_variant)));
+    if (resident) s.tpl = std::max(2, std::min(rtpl, golk::kResidentMaxTurns));
     if (blockable && s.tpl > 1 && big_buf && !c->tile_big)
         c->blocking_limited = true;   // reported in gol_info.blocking_limited
     if (!blockable || c->blocking_limited) s.tpl = 1;
@@ -492,7 +506,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
 
     DeviceGuard g(dev);
     (void)hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    s.band_multi = cfg->band_rows;
+    s.band_multi = resident ? rplan.rows : cfg->band_rows;   // (resident: the rows per lane)
     if (s.band_multi <= 0 && s.tpl > 1) {
         const int ncu = c->ncu;
         const int bpc = golk::multi_blocks_per_cu(s.tpl, c->multi_words, s.multi_variant);
@@ -538,7 +552,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     const bool small = blockable && s.tpl > 1 &&
                        (c->tile_only || (long long)c->buf_rows * c->pitch < (1ll << 20));
     const bool pinned = getenv("GOL_MULTI_VARIANT") != nullptr;
-    if (blockable && s.tpl > 1 &&
+    if (blockable && s.tpl > 1 && !resident &&
         ((small && !pinned && cfg->band_rows <= 0) || s.multi_variant == golk::kMultiTile))
         if (int rc2 = initial_tile_shape(c, cntb)) {
             // a tile_only board no tile shape fits (a few rows) and nothing pinned: one turn per
@@ -556,7 +570,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
         }
     const char *at = getenv("GOL_AUTOTUNE");
     bool tuning = !(cfg->flags & GOL_FLAG_NO_AUTOTUNE) && (!at || atoi(at) != 0) &&
-                  cfg->band_rows <= 0 && s.tpl > 1;
+                  cfg->band_rows <= 0 && s.tpl > 1 && !resident;
     // a BASELINE board size on an MI355X: the pinned shape, no search (GOL_AUTOTUNE=2: search);
     // the first engine of the shape in this process times it once (check_pinned: a warning
     // when slow, never a different shape)

@@ -84,13 +84,22 @@ enum : int {
                             //   K turns (engine-internal; tools build only)
     kMultiTileStream = 17,  // K1q k_tile_stream: blocks of K turns over (block, tile) items taken
                             //   in order by resident workgroups (engine-internal; tools build only)
-    kMultiInternalEnd = 18, // one past the engine-internal launch kinds (size of any table by kind)
+    kMultiResident = 18,    // K1r2 k_step_resident: a torus board narrower than 256 cells held
+                            //   whole in the registers of one workgroup for the launch's turns
+                            //   (engine-internal: GOL_FLAG_RESIDENT asks for it; gol_resident.h)
+    kMultiInternalEnd = 19, // one past the engine-internal launch kinds (size of any table by kind)
     kMultiAblate = 100,     // 100 + ABL mask: k_step_skew<8> timing ablations (K = 8 only)
 };
+// k_step_resident's depth: 2 .. kResidentMaxTurns turns per launch (the count ring's kRingAhead:
+// the slots of one counted launch are what one zeroing batch clears)
+constexpr int kResidentMaxTurns = 256;
+constexpr bool is_resident_variant(int v) { return v == kMultiResident; }
+constexpr bool resident_turns_ok(int turns) { return turns >= 2 && turns <= kResidentMaxTurns; }
 
 static_assert(kMultiTile < kMultiUserEnd && kMultiWgPgS < kMultiUserEnd,
               "every requestable variant lies below the engine-internal launch kinds");
 static_assert(kMultiTilePersist >= kMultiUserEnd && kMultiTileStream < kMultiInternalEnd &&
+              kMultiResident >= kMultiUserEnd && kMultiResident < kMultiInternalEnd &&
               kMultiInternalEnd < kMultiAblate, "engine-internal kinds between the two ranges");
 
 #ifndef GOL_TOOLS
@@ -201,6 +210,10 @@ int multi_blocks_per_cu(int turns, int words_per_lane, int variant);
 int pick_band_multi(int width, int rows, int lane_dwords, int turns, int capacity_waves,
                     int variant);
 hipError_t launch_step_multi(const StepArgs &a, int turns, hipStream_t s);
+// k_step_resident (gol_resident.hip): `turns` turns of the whole torus board a.in -> a.out in one
+// workgroup (a.counts: the counted form); hipErrorInvalidValue for a board, row range or depth
+// it does not run (gol_resident.h, resident_plan)
+hipError_t launch_resident(const StepArgs &a, int turns, hipStream_t s);
 // k_step_tile (gol_tile.hip): a launch of `turns` turns on tiles of band x tile_w words with
 // tile_seg rows per lane; shape check, workgroup waves, tile count
 constexpr int kTileMaxWavesHost = 16;  // k_step_tile: waves per workgroup (gol_tile.h)

@@ -282,17 +282,7 @@ __global__ __launch_bounds__(256) void k_step_ring(const uint64_t *__restrict__ 
 
 
 // ---------------------------------------------------- K1g: generic stencil
-__device__ __forceinline__ uint64_t west_word(const uint64_t *row, int j, int nw, int nb)
-{
-    const uint64_t carry = j > 0 ? (row[j - 1] >> 63) : ((row[nw - 1] >> (nb - 1)) & 1ull);
-    return (row[j] << 1) | carry;
-}
-__device__ __forceinline__ uint64_t east_word(const uint64_t *row, int j, int nw, int nb)
-{
-    if (j < nw - 1) return (row[j] >> 1) | (row[j + 1] << 63);
-    return (row[j] >> 1) | ((row[0] & 1ull) << (nb - 1));
-}
-
+// (west_word / east_word: gol_device.h)
 template <bool BLK, bool CNT>
 __global__ __launch_bounds__(256) void k_step_generic(const uint64_t *__restrict__ in,
                                                       uint64_t *__restrict__ out,
@@ -705,6 +695,7 @@ hipError_t launch_step(const StepArgs &a, bool fast, hipStream_t s)
 int multi_max_turns(int variant)
 {
     if (variant == kMultiTile) return kMaxTileTurns;
+    if (variant == kMultiResident) return kResidentMaxTurns;
     if (variant == kMultiWgHx || variant == kMultiWgPg) return GOL_TOOLS ? kWgDeepMax : 16;
     if (variant == kMultiWgHxS || variant == kMultiWgPgS) return 16;
     return is_wg_variant(variant) ? 16 : variant == kMultiSkewILW16 ? 12 : 8;
@@ -757,6 +748,7 @@ int auto_band_multi(int width, int rows, int lane_dwords)
 bool multi_ok(int width, int turns, int variant, int tile_code)
 {
     if (turns < 2 || turns > multi_max_turns(variant)) return false;
+    if (variant == kMultiResident) return width <= 255;  // (the height: resident_plan, at create)
     if (variant != kMultiTile) return fast_path_ok(width);
     // k_step_tile: any width of at least 256 cells.  Across the row seam (width % 64 != 0) only
     // the codes with a seam instantiation; an odd word count has no two-word lanes.
@@ -876,6 +868,7 @@ hipError_t launch_step_multi(const StepArgs &a, int turns, hipStream_t s)
 {
     if (a.row_hi <= a.row_lo) return hipSuccess;
     if (a.multi_variant == kMultiTile) return launch_tile(a, turns, s);
+    if (a.multi_variant == kMultiResident) return launch_resident(a, turns, s);
     if (!GOL_TOOLS && a.multi_words != 1) return hipErrorInvalidValue;   // tools build only
     return a.multi_words == 1 ? launch_multi_v<1>(a, turns, s) : launch_multi_v<2>(a, turns, s);
 }

@@ -94,13 +94,24 @@ int band_for_depth(gol_ctx *c, int k)
 }
 
 // A count engine (GOL_FLAG_COUNT_EVERY_TURN) runs multi-turn launches only on k_step_tile at
-// a code with a counted instantiation (golk::kTileCountCodes); every other count engine -- K1s
+// a code with a counted instantiation (golk::kTileCountCodes) and on k_step_resident (every
+// instantiation has its counted form); every other count engine -- K1s
 // / K1w kernels, a GOL_TILE code without one, generic widths, blocking_limited,
 // GOL_COUNT_BLOCKING=0 -- runs one-turn launches with the count fused into the stencil.
 bool count_fused(const gol_ctx *c)
 {
     return (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) && c->count_blocking && c->shape.tpl > 1 &&
-           c->shape.multi_variant == golk::kMultiTile && golk::tile_code_counted(c->shape.tile_seg);
+           (golk::is_resident_variant(c->shape.multi_variant) ||
+            (c->shape.multi_variant == golk::kMultiTile &&
+             golk::tile_code_counted(c->shape.tile_seg)));
+}
+
+// a k_step_resident launch of k turns (its one shape: the band is the create-time rows per lane,
+// whatever the depth); a depth it does not run: one turn
+Launch resident_launch(const gol_ctx *c, int k)
+{
+    if (!golk::resident_turns_ok(k)) return Launch{1, c->shape.multi_variant, c->band, 0, 0};
+    return Launch{k, golk::kMultiResident, c->shape.band_multi, 0, 0};
 }
 
 }  // namespace
@@ -135,6 +146,7 @@ Launch plan_launch(gol_ctx *c, int64_t room)
         if (room < 2) return L;
         const int64_t nl = (room + s.tpl - 1) / s.tpl;
         const int k = (int)((room + nl - 1) / nl);
+        if (golk::is_resident_variant(s.multi_variant)) return resident_launch(c, k);
         const int band = band_for_depth(c, k);
         if (!golk::multi_ok(c->cfg.width, k, s.multi_variant, s.tile_seg) ||
             !golk::tile_shape_ok(c->nw, k, band, s.tile_w, s.tile_seg, c->cfg.width))
@@ -149,6 +161,7 @@ Launch plan_launch(gol_ctx *c, int64_t room)
     }
     const int64_t nl = (room + s.tpl - 1) / s.tpl;
     const int k = (int)((room + nl - 1) / nl);
+    if (golk::is_resident_variant(s.multi_variant)) return resident_launch(c, k);
     if (!golk::multi_ok(c->cfg.width, k, s.multi_variant, s.tile_seg)) return L;
     const int band = band_for_depth(c, k);
     // (a big engine: no depth at which the tile's window would not fit -- one turn instead)
@@ -161,6 +174,7 @@ const std::vector<Launch> *timed_sequence(const gol_ctx *c, int64_t turns)
 {
     const auto &seq = c->shape.seq;
     const bool cnt = (c->cfg.flags & GOL_FLAG_COUNT_EVERY_TURN) != 0;
+    // (a resident engine has no timed sequence: nothing was timed for it)
     return !is_strip(c) && !cnt && !c->blocked_pending && turns >= 2 && turns <= kSeqMax &&
                    turns < (int64_t)seq.size() && !seq[turns].empty()
                ? &seq[turns]

@@ -222,7 +222,8 @@ def Run(p: Params, events: Channel, keyPresses: Optional[Channel] = None, *,
         devices: Optional[list] = None, halo: int = 0, ticker_ms: int = 2000,
         event_capacity: int = 1, emit_turn_complete: bool = True,
         emit_cell_flipped: bool = False, count_every_turn: bool = False,
-        alive_as_array: bool = False, resume: Optional[bool] = None) -> RunHandle:
+        alive_as_array: bool = False, resume: Optional[bool] = None,
+        resident: bool = False) -> RunHandle:
     """Start a run and return immediately (reference ``gol.Run``, Local/gol/gol.go:12-40).
 
     Events arrive on ``events`` in the reference's order
@@ -231,7 +232,9 @@ def Run(p: Params, events: Channel, keyPresses: Optional[Channel] = None, *,
     FinalTurnComplete, StateChange{T, Quitting}, ImageOutputComplete{T, "WxHxT"},
     then the channel is closed.  ``ngpus`` = number of row strips (the
     reference's ``len(SUB)``), one engine each.  ``resume`` = the reference's
-    ``CONT=yes`` (None: read the CONT environment variable).
+    ``CONT=yes`` (None: read the CONT environment variable).  ``resident`` asks the
+    engines for GOL_FLAG_RESIDENT (a board narrower than 256 cells held in one workgroup;
+    an engine that is not eligible runs as without it).
     """
     if devices is not None and len(devices) != int(ngpus):
         # gol_run_start reads devices[0..ngpus-1]
@@ -251,7 +254,8 @@ def Run(p: Params, events: Channel, keyPresses: Optional[Channel] = None, *,
     opts.event_capacity = int(event_capacity)
     opts.emit_turn_complete = 1 if emit_turn_complete else 0
     opts.emit_cell_flipped = 1 if emit_cell_flipped else 0
-    opts.engine_flags = N.GOL_FLAG_COUNT_EVERY_TURN if count_every_turn else 0
+    opts.engine_flags = ((N.GOL_FLAG_COUNT_EVERY_TURN if count_every_turn else 0) |
+                         (N.GOL_FLAG_RESIDENT if resident else 0))
     opts.resume = -1 if resume is None else (1 if resume else 0)
     h = ctypes.c_void_p()
     rc = L.gol_run_start(ctypes.byref(prm), ctypes.byref(opts), ctypes.byref(h))

@@ -33,6 +33,7 @@ GOL_CONTROL_STOP = 2
 GOL_FLAG_COUNT_EVERY_TURN = 0x1
 GOL_FLAG_FORCE_GENERIC = 0x2
 GOL_FLAG_NO_AUTOTUNE = 0x4
+GOL_FLAG_RESIDENT = 0x8
 
 GOL_EV_ALIVE_CELLS_COUNT = 1
 GOL_EV_IMAGE_OUTPUT_COMPLETE = 2
@@ -138,6 +139,9 @@ SIGNATURES = {
                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64)]),
     "gol_seam_word": (_i32, [ctypes.POINTER(ctypes.c_uint64), _i32, _i32, _i32,
                              ctypes.POINTER(ctypes.c_uint64)]),
+    "gol_resident_plan": (_i32, [_i32, _i32, ctypes.POINTER(ctypes.c_int32),
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "gol_resident_host_run": (_i32, [_u64p, _i32, _i32, _i32, _u64p, _i64p]),
     "gol_tile_persist_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_tile_stream_codes": (_i32, [ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "gol_stream_wait": (_i32, [_vp, _vp]),

@@ -82,6 +82,15 @@ typedef struct gol_ctx gol_ctx;
 #define GOL_FLAG_FORCE_GENERIC     0x2u  /* use the generic stencil even when the fast one applies */
 #define GOL_FLAG_NO_AUTOTUNE       0x4u  /* skip the create-time (turns per launch, band) timing
                                             sweep on large boards (results never depend on it) */
+#define GOL_FLAG_RESIDENT          0x8u  /* a request: run a torus board narrower than 256 cells
+                                            resident in the registers of one workgroup, up to 256
+                                            turns per launch (k_step_resident).  Eligible: halo ==
+                                            0, width <= 255, height <= 256 x floor(16 / words per
+                                            row) (4096, 2048, 1280, 1024 rows at 1 .. 4 words), no
+                                            GOL_FLAG_FORCE_GENERIC, turns_per_launch != 1.  Every
+                                            other engine runs as without the flag;
+                                            gol_info.turns_per_launch tells which it got (the
+                                            resident depth, or 1).  Results never depend on it. */
 
 typedef struct gol_config {
     int32_t  width;       /* Params.ImageWidth  (>= 2)                                   */
@@ -97,7 +106,8 @@ typedef struct gol_config {
                                   Widths of at least 256 cells block: multiples of 128 on
                                   every multi-turn kernel, the others on k_step_tile alone
                                   (gol_tile_seam_codes where width % 64 != 0); narrower
-                                  boards run one turn per launch.  A board buffer of 2 GiB
+                                  boards run one turn per launch unless GOL_FLAG_RESIDENT
+                                  (then 0 = 256, and 2 .. 256 are taken).  A board buffer of 2 GiB
                                   or more blocks on k_step_tile alone (gol_tile_big_codes),
                                   and only with width % 64 == 0 and no per-turn counts
                                   (gol_info.blocking_limited)                            */
@@ -111,7 +121,8 @@ typedef struct gol_info {
     int32_t  fast_path;         /* 1 = the LDS-free DPP stencil (width % 128 == 0, >= 256) */
     int32_t  band_rows;         /* effective band height                              */
     int32_t  halo_valid;        /* strip mode: turns left before the next exchange    */
-    int32_t  turns_per_launch;  /* effective temporal-blocking depth (1: widths below 256,
+    int32_t  turns_per_launch;  /* effective temporal-blocking depth (1: widths below 256
+                                   unless GOL_FLAG_RESIDENT took effect,
                                    forced-generic engines, count engines of a width that
                                    is no multiple of 128, blocking_limited)             */
     int32_t  device;
@@ -262,6 +273,22 @@ int gol_tile_window(int64_t modrows, int64_t pitch_words, int64_t y0, int32_t tu
  * GOL_EINVAL for a v outside that range, width < 256, an unknown layout or null pointers.
  * Needs no device. */
 int gol_seam_word(const uint64_t *row, int32_t width, int32_t v, int32_t layout, uint64_t *out);
+/* How k_step_resident (GOL_FLAG_RESIDENT) partitions a torus board of width x height cells over
+ * the lanes of its one workgroup: *lanes active lanes (1 .. 256) of *rows_per_lane consecutive
+ * rows each -- the last lane owns what is left, at least one row -- in *waves wavefronts
+ * (ceil(lanes / 64)); a lane holds rows_per_lane x ceil(width / 64) <= 16 words.  Needs no
+ * device.  GOL_EINVAL for a board that is not eligible by its shape (width < 2 or > 255, height
+ * < 1 or above 256 x floor(16 / words per row)) and for null pointers. */
+int gol_resident_plan(int32_t width, int32_t height, int32_t *lanes, int32_t *rows_per_lane,
+                      int32_t *waves);
+/* The host build of k_step_resident: `turns` turns (>= 0) of the torus board `in` (height rows of
+ * ceil(width / 64) words, standard layout, padding bits zero) into `out`, by the kernel's own
+ * functions -- the partition above, the in-lane west / east words, the row sums, the rule, the
+ * tail mask -- run lane by lane, with arrays indexed like the kernel's LDS exchange area (by lane
+ * modulo the active lanes, double-buffered by turn parity).  counts: NULL, or `turns` entries,
+ * the alive cells after each turn.  Needs no device.  GOL_EINVAL as gol_resident_plan. */
+int gol_resident_host_run(const uint64_t *in, int32_t width, int32_t height, int32_t turns,
+                          uint64_t *out, int64_t *counts);
 /* The subset of those the persistent tile kernel (K1p: small torus boards, tiles resident
  * across blocks of turns) runs; same convention. */
 int gol_tile_persist_codes(int32_t *codes, int32_t cap);
