@@ -87,8 +87,92 @@ __device__ __forceinline__ void tile_turn_asm(uint32_t (&v)[SEG][2], uint32_t (&
 #endif
 template <int SEG, int W>
 constexpr bool tile_west_carry() { return GOL_TILE_WEST_CARRY && W == 1 && SEG >= 4 && SEG <= 16; }
+// VGPR parity pins (tile_parity_pins below; 0: the compiler's own register numbers, A/B builds:
+// make variant VDEFS=-DGOL_TILE_PARITY_PINS=0)
+#ifndef GOL_TILE_PARITY_PINS
+#define GOL_TILE_PARITY_PINS 1
+#endif
 
 namespace golk {
+
+// vpin<N>(x): from here on x lives in VGPR N.  An empty asm statement whose operand is tied to
+// the physical register: it emits nothing, the compiler writes x's definition straight into vN
+// and goes on scheduling the instructions around it.  (Register names are string literals:
+// hence a table, indexed at compile time from the pinned turn's unrolled rows.)
+template <int N>
+__device__ __forceinline__ void vpin(uint32_t &x);
+#define GOL_VPIN(N)                                                                               \
+    template <>                                                                                   \
+    __device__ __forceinline__ void vpin<N>(uint32_t &x) { asm("" : "+{v" #N "}"(x)); }
+#define GOL_VPIN8(A, B, C, D, E, F, G, H)                                                         \
+    GOL_VPIN(A) GOL_VPIN(B) GOL_VPIN(C) GOL_VPIN(D) GOL_VPIN(E) GOL_VPIN(F) GOL_VPIN(G) GOL_VPIN(H)
+GOL_VPIN8(0, 1, 2, 3, 4, 5, 6, 7)
+GOL_VPIN8(8, 9, 10, 11, 12, 13, 14, 15)
+GOL_VPIN8(16, 17, 18, 19, 20, 21, 22, 23)
+GOL_VPIN8(24, 25, 26, 27, 28, 29, 30, 31)
+GOL_VPIN8(32, 33, 34, 35, 36, 37, 38, 39)
+GOL_VPIN8(40, 41, 42, 43, 44, 45, 46, 47)
+GOL_VPIN8(48, 49, 50, 51, 52, 53, 54, 55)
+GOL_VPIN8(56, 57, 58, 59, 60, 61, 62, 63)
+GOL_VPIN8(64, 65, 66, 67, 68, 69, 70, 71)
+GOL_VPIN8(72, 73, 74, 75, 76, 77, 78, 79)
+#undef GOL_VPIN8
+#undef GOL_VPIN
+
+// The register plan of a pinned turn (ORD 5's turn4, one word per lane, SEG even).  A
+// v_bitop3_b32 whose three source VGPRs share one register-number parity issues at half rate
+// ("VGPR parity pins"), and the compiler does not number registers by parity.  The
+// plan names a register for every value whose parity decides a triple; everything else --
+// wl, er, lm, g1, g2, the LDS addresses, what ds_read returns -- stays the compiler's.
+//   cells   row i: even dword v(2i), odd dword v(2i+1).  (wl, e, o) and (e, o, er) are mixed
+//           whatever wl and er get.
+//   sums    row j's sum k has parity (j + k) & 1: the rule's (a, b, c) triples read rows
+//           j-1, j, j+1, so two of one parity and one of the other.  Five 4-register sets
+//           from v(2 SEG) on: A0, A1 (even rows, sum k in base + k), B0, B1 (odd rows from 3
+//           on, sum k in base + (k ^ 1)), S (row 1, as B: its sums stay live to the end of the
+//           turn for row 0's rule).  Row j takes set (j >> 1) & 1 of its class, so the three
+//           rows of a window never share a set.
+//   LDS     put stores one even-aligned 4-register tuple and get returns one, so position q of
+//           a slot has parity q & 1.  Row 0 (class A) is stored in order.  Row SEG - 1 is odd:
+//           the bottom-edge array holds its sums in the order 1, 0, 3, 2, which is how set B
+//           holds them -- no copy before the put, and what get returns from that array (the
+//           row above the segment, the segment's own last row) has class B's parities.  Then
+//           row 0's rule reads (U: B, F: A, S1: B) and row SEG - 1's (row SEG - 2: A, Lr: B,
+//           D: A): the chain closes at both ends.
+//   rule    per dword d (centre C = the cell, parity d): lx and hm opposite to C, hx opposite
+//           to lx; then (lm, lx, C), (hm, C, g1) and (lx, hx, g2) are mixed whatever lm, g1,
+//           g2 get.  Two of the three take the registers of the donor, the row whose sums die
+//           in this rule (row i - 1; for row 0 the kept sums of row 1): its sums 2d and 2d + 1
+//           sit in an even / odd pair.  The one with C's parity takes hx.  If that is sum
+//           2d + 1's, lx overwrites sum 2d in place (after lm) and hx sum 2d + 1 (after hm);
+//           else hx overwrites sum 2d (after lm and lx) and hm sum 2d + 1 (after hx).  The
+//           third value (hm, resp. lx) takes one register per dword after the sums.  Row 2 has
+//           no donor (row 1's sums stay live for row 0's rule): lx and hm take that register
+//           and a second one, hx the cell's own register once g2 has read the centre.
+//           Naming the donor's registers rather than a fixed set for all rows keeps the
+//           rules of consecutive rows independent: with four fixed registers and hx always in
+//           the cell the loop was as clean and no faster than the compiler's.
+// tools/vgpr_parity.py counts the triples in the compiled loop; tests/test_tile_parity_cpu.py
+// asserts the count is zero.
+constexpr int tile_pin_cell(int i, int d) { return 2 * i + d; }
+constexpr int tile_pin_sum(int seg, int j, int k)
+{
+    const int base = 2 * seg + (j == 1 ? 16 : (j & 1) * 8 + ((j >> 1) & 1) * 4);
+    return base + ((j & 1) ? k ^ 1 : k);
+}
+// (t: 0 the third value of a rule, 1 row 2's second one)
+constexpr int tile_pin_tmp(int seg, int d, int t) { return 2 * seg + 20 + 2 * t + (d ^ 1); }
+// Which instantiations run the plan: the 65536^2-class segment in its plain and counted forms
+// (tools/vgpr_parity.py: 43 and 117 same-parity v_bitop3 of 288 without it; +3 % on the bench,
+// -10 % per turn on a count engine).  Not the big form: its loop is as clean under the plan
+// (25 -> 0) and ran 11 % slower at 65536^2, 122.9-123.1k against 138.5-139.2k GCUPS under
+// GOL_TILE_BIG=1 ("VGPR parity pins").
+template <int SEG, int ORD, int W, bool PERSIST, bool RING, bool CNT, bool SEAM, bool BIG>
+constexpr bool tile_parity_pins()
+{
+    return GOL_TILE_PARITY_PINS && ORD == 5 && W == 1 && !PERSIST && !RING && !SEAM && !BIG &&
+           SEG == 16;
+}
 
 constexpr int kTileMaxWaves = 16;                       // 1024 threads per workgroup
 // dynamic LDS of a workgroup of `threads` threads: row sums of the segments' edge rows (16 B
@@ -243,6 +327,9 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     constexpr int ND = 2 * W;                            // dwords per lane and row
     constexpr int NS = 2 * ND;                           // row-sum dwords (2 bits per dword)
     static_assert(SEG >= 2, "two edge rows per segment");
+    constexpr bool kPins = tile_parity_pins<SEG, ORD, W, PERSIST, RING, CNT, SEAM, BIG>();
+    static_assert(!kPins || (SEG % 2 == 0 && SEG >= 4 && 2 * SEG + 24 <= 80),
+                  "pinned turns: an even segment (the plan's last row is odd), registers below v80");
     // per turn parity: the 3-cell row sums of the first / last row of every segment,
     // segment-major, C slots per segment (dynamic LDS, W uint4 per slot)
     extern __shared__ uint4 xsh[];
@@ -784,7 +871,130 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
         get(wbot(p, off), F);                                 // (Lr)
         rule(Pw, F, D, v[SEG - 1]);
     };
+    // ORD 5's turn under the register plan (tile_parity_pins, above): the same instructions in
+    // the same order as turn4, the rows indexed at compile time so that each value can name
+    // its register.  The bottom-edge array holds its sums in the order 1, 0, 3, 2 (swz).
+    [[maybe_unused]] auto turn4p = [&](auto P, int poff) {
+        if constexpr (kPins) {
+            constexpr int p = decltype(P)::value;
+            const int off = poff;
+            auto swz = [](uint32_t (&S)[NS]) {
+                const uint32_t s0 = S[0], s2 = S[2];
+                S[0] = S[1];
+                S[1] = s0;
+                S[2] = S[3];
+                S[3] = s2;
+            };
+            auto rsum_p = [&](auto J, uint32_t (&S)[NS]) {
+                constexpr int j = decltype(J)::value;
+                rsum(v[j], S);
+                vpin<tile_pin_sum(SEG, j, 0)>(S[0]);
+                vpin<tile_pin_sum(SEG, j, 1)>(S[1]);
+                vpin<tile_pin_sum(SEG, j, 2)>(S[2]);
+                vpin<tile_pin_sum(SEG, j, 3)>(S[3]);
+            };
+            auto rule_d = [&](auto I, auto Dw, const uint32_t (&A)[NS], const uint32_t (&B)[NS],
+                              const uint32_t (&Cs)[NS]) {
+                constexpr int i = decltype(I)::value, d = decltype(Dw)::value;
+                // the donor: the row whose sums die in this rule (the plan's comment, above)
+                constexpr int jd = i == 0 ? 1 : i - 1;
+                constexpr int r0 = tile_pin_sum(SEG, jd, 2 * d), r1 = tile_pin_sum(SEG, jd, 2 * d + 1);
+                constexpr int rt = tile_pin_tmp(SEG, d, 0);
+                const uint32_t Cc = v[i][d];
+                const uint32_t lm = maj(A[2 * d], B[2 * d], Cs[2 * d]);
+                uint32_t lx = bitop3<0x7e>(A[2 * d], B[2 * d], Cs[2 * d]);
+                uint32_t hm, hx;
+                if constexpr (i == 2) {
+                    // (row 1's sums stay live for row 0's rule: no donor; hx takes the cell's own
+                    // register, free once g2 has read the centre)
+                    vpin<rt>(lx);
+                    hm = maj(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<tile_pin_tmp(SEG, d, 1)>(hm);
+                    const uint32_t g1 = bitop3<0x16>(lm, lx, Cc);
+                    const uint32_t g2 = bitop3<0x86>(hm, Cc, g1);
+                    hx = xor3(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<tile_pin_cell(i, d)>(hx);
+                    uint32_t n = bitop3<0x82>(lx, hx, g2);
+                    vpin<tile_pin_cell(i, d)>(n);
+                    return n;
+                } else if constexpr ((r1 & 1) == d) {
+                    vpin<r0>(lx);
+                    hm = maj(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<rt>(hm);
+                    hx = xor3(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<r1>(hx);
+                } else {
+                    vpin<rt>(lx);
+                    hx = xor3(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<r0>(hx);
+                    hm = maj(A[2 * d + 1], B[2 * d + 1], Cs[2 * d + 1]);
+                    vpin<r1>(hm);
+                }
+                const uint32_t g1 = bitop3<0x16>(lm, lx, Cc);
+                const uint32_t g2 = bitop3<0x86>(hm, Cc, g1);
+                uint32_t n = bitop3<0x82>(lx, hx, g2);       // (life_rule7)
+                vpin<tile_pin_cell(i, d)>(n);
+                return n;
+            };
+            auto rule_p = [&](auto I, const uint32_t (&A)[NS], const uint32_t (&B)[NS],
+                              const uint32_t (&Cs)[NS]) {
+                constexpr int i = decltype(I)::value;
+                const uint32_t n0 = rule_d(I, std::integral_constant<int, 0>{}, A, B, Cs);
+                const uint32_t n1 = rule_d(I, std::integral_constant<int, 1>{}, A, B, Cs);
+                v[i][0] = n0;
+                v[i][1] = n1;
+            };
+            uint32_t Pw[NS], Q[NS], S1[NS];
+            {
+                uint32_t F[NS], Lr[NS];
+                rsum_p(std::integral_constant<int, 0>{}, F);
+                rsum_p(std::integral_constant<int, SEG - 1>{}, Lr);
+                put(wtop(p, off), F);
+                swz(Lr);
+                put(wbot(p, off), Lr);
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < NS; ++k) Pw[k] = F[k];
+            }
+            rsum_p(std::integral_constant<int, 1>{}, Q);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) S1[k] = Q[k];
+            unroll_seq(std::make_integer_sequence<int, SEG - 2>{}, [&](auto I0) {
+                constexpr int i = decltype(I0)::value + 1;
+                uint32_t R[NS];
+                if constexpr (i + 2 == SEG) {
+                    get(wbot(p, off), R);                    // (own bottom slot: Lr)
+                    swz(R);
+                } else {
+                    rsum_p(std::integral_constant<int, i + 1>{}, R);
+                }
+                rule_p(std::integral_constant<int, i>{}, Pw, Q, R);
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    Pw[k] = Q[k];
+                    Q[k] = R[k];
+                }
+            });
+#pragma unroll
+            for (int i = 1; i + 1 < SEG; ++i)
+#pragma unroll
+                for (int d = 0; d < ND; ++d) asm volatile("" : "+v"(v[i][d]));
+            uint32_t U[NS], D[NS], F[NS];
+            get(rup(p, off), U);
+            swz(U);
+            get(wtop(p, off), F);
+            rule_p(std::integral_constant<int, 0>{}, U, F, S1);
+            get(rdn(p, off), D);
+            get(wbot(p, off), F);                            // (Lr)
+            swz(F);
+            rule_p(std::integral_constant<int, SEG - 1>{}, Pw, F, D);
+        }
+    };
     auto turn = [&](auto P, int poff, int t) {
+        if constexpr (kPins) {
+            turn4p(P, poff);
+            return;
+        }
         if constexpr (ORD >= 4) {
             turn4(P, poff, t, kHalo && wave == 0 ? min(t + 1, SEG - 2) : 0);
             return;
@@ -895,6 +1105,15 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
             rule(Pw, Lr, D, v[SEG - 1]);
         }
     };
+    // (the plan's cell registers from the first turn on: loop-carried values tied to one
+    // register at the loop's head and at their redefinition need no copy)
+    if constexpr (kPins) {
+        unroll_seq(std::make_integer_sequence<int, SEG>{}, [&](auto I) {
+            constexpr int i = decltype(I)::value;
+            vpin<tile_pin_cell(i, 0)>(v[i][0]);
+            vpin<tile_pin_cell(i, 1)>(v[i][1]);
+        });
+    }
     const int lastrow = 2 * K + TH - 1;
     // a wave leaving the trapezoid at turn t: its rows are all < K or >= K + TH, so it has
     // nothing to store.  It ends (the barrier stops counting it; ORD 4: its flag says it has
