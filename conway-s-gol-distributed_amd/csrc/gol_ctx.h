@@ -140,6 +140,9 @@ struct gol_ctx {
     // a buffer), or GOL_TILE_BIG=1 at create on a buffer of any size.  tile_big_forced: the
     // latter, which also goes to the launches (StepArgs::tile_big)
     bool tile_big = false, tile_big_forced = false;
+    // plain k_step_tile launches of a code with a pair form run it (k_step_tile_duo,
+    // StepArgs::tile_duo): set at create unless GOL_TILE_DUO=0
+    bool tile_duo = false;
     int band = 8;
     int variant = golk::kVariantDefault;
     int multi_words = 2;                     // k_step_multi words per lane

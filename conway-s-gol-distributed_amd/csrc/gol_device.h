@@ -152,6 +152,34 @@ __device__ __forceinline__ uint32_t life_rule7(uint32_t a0, uint32_t b0, uint32_
     const uint32_t g2 = bitop3<0x86>(hm, C, g1);
     return bitop3<0x82>(lx, hx, g2);
 }
+// Two vertically adjacent output rows i and i + 1 share the rows i and i + 1 of their windows.
+// life_pair_sum: that pair's sum P = b + c (0 .. 6) in binary, from the 2-bit row sums b of row i
+// and c of row i + 1, formed once: 4 ops, two of them VOP2 (full rate whatever the registers).
+// life_rule_pair: one output from P, the sums a of its window's third row (row i - 1 for output
+// i, row i + 2 for output i + 1) and its centre cell x: 4 ops.  12 ops per pair of rows instead
+// of life_rule7's 14.  T = a + P counts the window with the centre; next = (T == 3) | (x & T == 4).
+//   u = x ? a0 | p0 : a0 ^ p0;  w = 1 for (a1, p1, p2) in {010, 100, 111};  z = x & (a1 == p1);
+//   next = 1 for (u, w, z) in {001, 110}.
+// The tables rely on two facts: x = 1 implies a centre row sum >= 1 and x = 0 one <= 2, which
+// hold because the centre row's sum includes the centre.  Found by a search over fan-out-free
+// LUT3 trees; checked on all 4096 windows of 4 rows x 3 cells, both outputs, by
+// tests/test_pair_rule_cpu.py.
+__device__ __forceinline__ void life_pair_sum(uint32_t b0, uint32_t c0, uint32_t b1, uint32_t c1,
+                                              uint32_t &p0, uint32_t &p1, uint32_t &p2)
+{
+    const uint32_t k = b0 & c0;
+    p0 = b0 ^ c0;
+    p1 = xor3(b1, c1, k);
+    p2 = maj(b1, c1, k);
+}
+__device__ __forceinline__ uint32_t life_rule_pair(uint32_t a0, uint32_t a1, uint32_t p0,
+                                                   uint32_t p1, uint32_t p2, uint32_t x)
+{
+    const uint32_t u = bitop3<0xbc>(a0, p0, x);
+    const uint32_t w = bitop3<0x94>(a1, p1, p2);
+    const uint32_t z = bitop3<0x82>(a1, p1, x);
+    return bitop3<0x42>(u, w, z);
+}
 
 template <typename F, int... Is>
 __device__ __forceinline__ void unroll_seq(std::integer_sequence<int, Is...>, F &&f)

@@ -441,6 +441,7 @@ int gol_create_ex(const gol_config *cfg, gol_ctx **out)
     // a buffer of 2 GiB or more: the big form of K1t alone blocks it, on whole-word rows of >= 256
     // cells and with no counts (it has neither a seam nor a counted form).  GOL_TILE_BIG=1 (tests,
     // A/B runs) forces the form on a buffer of any size, and fails the create where it cannot run.
+    c->tile_duo = golk::tile_duo_env();
     const char *tb = getenv("GOL_TILE_BIG");
     c->tile_big_forced = tb && atoi(tb) != 0;
     const bool big_buf = !golk::multi_fits(c->nw, c->pitch, c->buf_rows);

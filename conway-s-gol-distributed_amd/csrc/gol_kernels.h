@@ -46,6 +46,10 @@ struct StepArgs {
     // lane segment
     int tile_w;
     int tile_seg;
+    // k_step_tile: 1 = plain launches of a code with a pair form run it (k_step_tile_duo: the
+    // interior rows ruled in pairs on shared row-pair sums).  The engine sets it at create unless
+    // GOL_TILE_DUO=0; 0 (a StepArgs built elsewhere): the plain kernel.
+    int tile_duo;
 };
 
 // device error codes (StepArgs::err)
@@ -439,6 +443,8 @@ __host__ __device__ inline uint64_t seam_stitch(uint64_t p, uint64_t s, int v, i
 bool tile_shape_ok(int nw, int turns, int tile_h, int tile_w, int seg, int width = 0);
 int tile_waves(int turns, int tile_h, int tile_w, int seg);
 // resident workgroups per CU of that launch (occupancy API: VGPRs, LDS; 0 on error)
+// (of the form launch_tile picks for a plain launch: the seam kernel by the width, the pair form
+// by tile_duo_env, below)
 int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg, int width = 0);
 // (gol_tile_seam.hip) the k_step_tile_seam instantiation of a code, or nullptr
 void *tile_seam_kernel(int code);
@@ -459,6 +465,12 @@ struct TileGrid {
 TileGrid tile_grid(int nw, int rows, int turns, int tile_h, int tile_w, int seg);
 // (gol_tile_big.hip) the k_step_tile_big instantiation of a code, or nullptr
 void *tile_big_kernel(int code);
+// (gol_tile_duo.hip) the k_step_tile_duo instantiation of a code, or nullptr
+void *tile_duo_kernel(int code);
+// GOL_TILE_DUO in the environment: unset or non-zero = the pair form where a code has one, 0 =
+// the plain kernel everywhere (A/B runs).  Read at create (Ctx::tile_duo) and by
+// tile_blocks_per_cu, which the planner and the tile search ask at create too.
+bool tile_duo_env();
 // tile_grid for a launch of the big form: the narrow column's tiles no taller than max_h
 // (tile_big_max_h: their window, too, wraps at most once and stays below 2 GiB) -- more of
 // them, or no repack when that saves no workgroup.  A real board of 2 GiB or more has far more

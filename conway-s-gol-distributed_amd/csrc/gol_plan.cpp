@@ -32,6 +32,7 @@ golk::StepArgs whole_buffer_args(const gol_ctx *c)
     a.multi_words = c->multi_words;
     a.wg_prio = c->wg_prio;
     a.tile_big = c->tile_big_forced ? 1 : 0;
+    a.tile_duo = c->tile_duo ? 1 : 0;
     a.err = c->d_err;
     return a;
 }

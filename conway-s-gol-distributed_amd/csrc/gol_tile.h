@@ -317,8 +317,17 @@ struct RingArgs {
 // (gol_kernels.h, tile_window) -- a 64-bit base formed on the scalar unit, 32-bit offsets within
 // the window, num_records the window's bytes.  Again only the load and the store stage differ
 // (below); one word per lane, plain launches, whole-word rows, no counts.
+// DUO (k_step_tile_duo: ORD 5's turn with the interior rows ruled in pairs): rows i and i + 1 of
+// the pairs (1, 2), (3, 4), .., (SEG - 3, SEG - 2) share the binary sum of their two rows' sums
+// (gol_device.h, life_pair_sum / life_rule_pair): 12 operations per pair and dword instead of
+// 2 x life_rule7's 7.  Rows 0 and SEG - 1 keep life_rule7 on the sums turn4 has live at the end
+// of the turn.  Only the turn differs (turn4d below): the loads, the LDS exchange, the barrier
+// and the stores are the plain kernel's.  One word per lane, plain launches, whole-word rows.
+// The registers are the compiler's: 47 of the loop's 232 v_bitop3 read three VGPRs of one
+// parity.  A plan in the manner of tile_parity_pins brought that to 0 at the same 328 VALU and
+// 64 VGPRs and measured no faster ("Shared row-pair sums"), so none is kept.
 template <int SEG, int ORD, int W, bool PERSIST, bool RING = false, bool CNT = false,
-          bool SEAM = false, bool BIG = false>
+          bool SEAM = false, bool BIG = false, bool DUO = false>
 __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
                                           uint64_t *__restrict__ out, const StepArgs &a,
                                           int turns, const TilePos &pos,
@@ -327,7 +336,10 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
     constexpr int ND = 2 * W;                            // dwords per lane and row
     constexpr int NS = 2 * ND;                           // row-sum dwords (2 bits per dword)
     static_assert(SEG >= 2, "two edge rows per segment");
-    constexpr bool kPins = tile_parity_pins<SEG, ORD, W, PERSIST, RING, CNT, SEAM, BIG>();
+    constexpr bool kPins = !DUO && tile_parity_pins<SEG, ORD, W, PERSIST, RING, CNT, SEAM, BIG>();
+    static_assert(!DUO || (ORD == 5 && W == 1 && SEG % 2 == 0 && SEG >= 4 && !PERSIST && !RING &&
+                           !CNT && !SEAM && !BIG),
+                  "pair turns: ORD 5, an even segment (whole pairs between the two edge rows)");
     static_assert(!kPins || (SEG % 2 == 0 && SEG >= 4 && 2 * SEG + 24 <= 80),
                   "pinned turns: an even segment (the plan's last row is odd), registers below v80");
     // per turn parity: the 3-cell row sums of the first / last row of every segment,
@@ -990,7 +1002,70 @@ __device__ __forceinline__ void tile_pass(const uint64_t *__restrict__ in,
             rule_p(std::integral_constant<int, SEG - 1>{}, Pw, F, D);
         }
     };
+    // DUO: turn4 with the interior rows in pairs.  A, B: the sums of the row above the pair and
+    // of its first row; per pair the sums of its second row and of the row below it are formed
+    // (the last pair's: read back from the own bottom slot), then the pair goes dword by dword --
+    // dword d needs only the sums 2d and 2d + 1, so one dword's P and temporaries are live at a
+    // time.
+    [[maybe_unused]] auto turn4d = [&](auto P, int poff) {
+        if constexpr (DUO) {
+            constexpr int p = decltype(P)::value;
+            const int off = poff;
+            uint32_t A[NS], B[NS], S1[NS];
+            {
+                uint32_t F[NS], Lr[NS];
+                rsum(v[0], F);
+                rsum(v[SEG - 1], Lr);
+                put(wtop(p, off), F);
+                put(wbot(p, off), Lr);
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < NS; ++k) A[k] = F[k];
+            }
+            rsum(v[1], B);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) S1[k] = B[k];
+#pragma unroll
+            for (int i = 1; i + 1 < SEG; i += 2) {
+                uint32_t Cs[NS], Dn[NS];
+                rsum(v[i + 1], Cs);
+                if (i + 3 == SEG) get(wbot(p, off), Dn);   // (own bottom slot: Lr)
+                else rsum(v[i + 2], Dn);
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    uint32_t p0, p1, p2;
+                    life_pair_sum(B[2 * d], Cs[2 * d], B[2 * d + 1], Cs[2 * d + 1], p0, p1, p2);
+                    const uint32_t n0 = life_rule_pair(A[2 * d], A[2 * d + 1], p0, p1, p2, v[i][d]);
+                    const uint32_t n1 =
+                        life_rule_pair(Dn[2 * d], Dn[2 * d + 1], p0, p1, p2, v[i + 1][d]);
+                    v[i][d] = n0;
+                    v[i + 1][d] = n1;
+                }
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    A[k] = Cs[k];
+                    B[k] = Dn[k];
+                }
+            }
+            // (A: the sums of row SEG - 2)
+#pragma unroll
+            for (int i = 1; i + 1 < SEG; ++i)
+#pragma unroll
+                for (int d = 0; d < ND; ++d) asm volatile("" : "+v"(v[i][d]));
+            uint32_t U[NS], D[NS], F[NS];
+            get(rup(p, off), U);
+            get(wtop(p, off), F);
+            rule(U, F, S1, v[0]);
+            get(rdn(p, off), D);
+            get(wbot(p, off), F);                            // (Lr)
+            rule(A, F, D, v[SEG - 1]);
+        }
+    };
     auto turn = [&](auto P, int poff, int t) {
+        if constexpr (DUO) {
+            turn4d(P, poff);
+            return;
+        }
         if constexpr (kPins) {
             turn4p(P, poff);
             return;
@@ -1686,6 +1761,20 @@ __global__ __launch_bounds__(1024, (SEG <= 16 ? 8 : 6)) void k_step_tile_big(
     const int tile = tile_of_block(L.ntiles);
     if (tile >= L.ntiles) return;                        // the whole workgroup
     tile_pass<SEG, ORD, 1, false, false, false, false, true>(in, out, a, turns, tile_pos(a, L, tile));
+}
+
+// k_step_tile with the interior rows ruled in pairs (tile_pass DUO; the instantiations:
+// gol_tile_duo.hip).  Its own entry point: the other kernels stay as they are.  The plain
+// kernel's grid, LDS bytes, TileLaunch and launch bounds.
+template <int SEG, int ORD, int W>
+__global__ __launch_bounds__(1024, 1) void k_step_tile_duo(const uint64_t *__restrict__ in,
+                                                           uint64_t *__restrict__ out, StepArgs a,
+                                                           int turns, TileLaunch L)
+{
+    const int tile = tile_of_block(L.ntiles);
+    if (tile >= L.ntiles) return;                        // the whole workgroup
+    tile_pass<SEG, ORD, W, false, false, false, false, false, true>(in, out, a, turns,
+                                                                    tile_pos(a, L, tile));
 }
 
 // k_step_tile with the per-turn alive counts fused (tile_pass CNT; the instantiations:

@@ -250,24 +250,33 @@ int tile_waves(int turns, int tile_h, int tile_w, int seg)
     return (nseg + G - 1) / G;
 }
 
+bool tile_duo_env()
+{
+    const char *e = getenv("GOL_TILE_DUO");
+    return !e || atoi(e) != 0;
+}
+
 int tile_blocks_per_cu(int turns, int tile_h, int tile_w, int seg, int width)
 {
     const bool seam = width > 0 && width % 64 != 0;      // (the seam kernel's own registers)
-    void *fn = seam ? tile_seam_kernel(seg) : tile_kernel(seg);
+    // (the pair form's, where it launches)
+    const bool duo = !seam && tile_duo_kernel(seg) && tile_duo_env();
+    void *fn = seam ? tile_seam_kernel(seg) : duo ? tile_duo_kernel(seg) : tile_kernel(seg);
     if (!fn) return 0;
     const int waves = tile_waves(turns, tile_h, tile_w, seg);
     if (waves < 1 || waves > kTileMaxWaves) return 0;
     // (the planner asks for thousands of shapes: cache per (kernel, waves))
     static std::mutex mu;
-    static std::map<std::tuple<int, int, bool>, int> cache;
+    static std::map<std::tuple<int, int, int>, int> cache;
     std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find({seg, waves, seam});
+    const int form = seam ? 1 : duo ? 2 : 0;
+    auto it = cache.find({seg, waves, form});
     if (it != cache.end()) return it->second;
     int blocks = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &blocks, fn, 64 * waves, tile_lds_bytes_code(64 * waves, seg)) != hipSuccess)
         blocks = 0;
-    cache[{seg, waves, seam}] = blocks;
+    cache[{seg, waves, form}] = blocks;
     return blocks;
 }
 
@@ -351,9 +360,13 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
     // kernel with the counts dropped)
     // a width that is no multiple of 64: the seam kernel (which has no counted form)
     const bool seam = a.width % 64 != 0;
+    // a plain launch (not big, seam or counted) of a code with a pair form, unless switched off:
+    // k_step_tile_duo, on the plain kernel's grid, LDS bytes and arguments
+    void *const duo = a.tile_duo ? tile_duo_kernel(a.tile_seg) : nullptr;
     void *fn = big    ? tile_big_kernel(a.tile_seg)
                : seam ? (a.counts ? nullptr : tile_seam_kernel(a.tile_seg))
                : a.counts ? tile_cnt_kernel(a.tile_seg)
+               : duo      ? duo
                           : tile_kernel(a.tile_seg);
     if (!fn || (a.counts && !tile_code_counted(a.tile_seg))) return hipErrorInvalidValue;
     StepArgs args = a;
