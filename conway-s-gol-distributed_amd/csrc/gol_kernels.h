@@ -250,11 +250,21 @@ constexpr int kTilePersistCodes[] = {102, 103, 104, 106, 108, 112, 116,
 constexpr int kTileStreamCodes[] = {106, 506, 512, 524};
 // the codes k_tile_ring (K1r) is instantiated for in the tools build (gol_tile.hip ring_fn)
 constexpr int kTileRingCodes[] = {103, 203, 503, 504, 506, 508, 512, 516, 112, 116};
-constexpr bool tile_code_shipped(int code)
+// (membership in one of the code sets here, and: every code of a set ships, one word per lane)
+template <int N>
+constexpr bool tile_code_in(const int (&set)[N], int code)
 {
-    for (int c : kTileCodes)
+    for (int c : set)
         if (c == code) return true;
     return false;
+}
+constexpr bool tile_code_shipped(int code) { return tile_code_in(kTileCodes, code); }
+template <int N>
+constexpr bool tile_codes_shipped_w1(const int (&set)[N])
+{
+    for (int c : set)
+        if (!tile_code_shipped(c) || c >= 1000) return false;
+    return true;
 }
 // the codes k_step_tile_cnt is instantiated for (gol_tile.hip tile_cnt_kernel): K1t with the
 // per-turn alive counts fused, what a GOL_FLAG_COUNT_EVERY_TURN engine's multi-turn launches
@@ -269,19 +279,8 @@ constexpr int kTileCountCodes[] = {
     503, 504, 506, 508, 512, 516, 524,                                           // ORD 5
     616,                                                                         // ORD 6
 };
-constexpr bool tile_code_counted(int code)
-{
-    for (int c : kTileCountCodes)
-        if (c == code) return true;
-    return false;
-}
-constexpr bool tile_count_codes_shipped()
-{
-    for (int c : kTileCountCodes)
-        if (!tile_code_shipped(c) || c >= 1000) return false;
-    return true;
-}
-static_assert(tile_count_codes_shipped(), "kTileCountCodes: a subset of kTileCodes, W = 1");
+constexpr bool tile_code_counted(int code) { return tile_code_in(kTileCountCodes, code); }
+static_assert(tile_codes_shipped_w1(kTileCountCodes), "kTileCountCodes: a subset of kTileCodes, W = 1");
 // the codes k_step_tile_seam is instantiated for (gol_tile_seam.hip tile_seam_kernel): K1t on a
 // board whose width is no multiple of 64, where the torus seam in x falls inside the row's last
 // word (tile_pass SEAM, seam_stitch below).  One word per lane, plain launches, no counted form.
@@ -295,19 +294,8 @@ constexpr int kTileSeamCodes[] = {
     102, 104, 106, 108, 112, 116,                                                // ORD 1
     516, 524,                                                                    // ORD 5
 };
-constexpr bool tile_code_seam(int code)
-{
-    for (int c : kTileSeamCodes)
-        if (c == code) return true;
-    return false;
-}
-constexpr bool tile_seam_codes_shipped()
-{
-    for (int c : kTileSeamCodes)
-        if (!tile_code_shipped(c) || c >= 1000) return false;
-    return true;
-}
-static_assert(tile_seam_codes_shipped(), "kTileSeamCodes: a subset of kTileCodes, W = 1");
+constexpr bool tile_code_seam(int code) { return tile_code_in(kTileSeamCodes, code); }
+static_assert(tile_codes_shipped_w1(kTileSeamCodes), "kTileSeamCodes: a subset of kTileCodes, W = 1");
 // the codes k_step_tile_big is instantiated for (gol_tile_big.hip tile_big_kernel): K1t on a
 // buffer of 2 GiB or more, whose rows a 32-bit byte offset from the buffer's start no longer
 // reaches (tile_pass BIG, tile_window below).  One word per lane, plain launches, whole-word
@@ -321,19 +309,8 @@ constexpr int kTileBigCodes[] = {
     512, 516, 524,                                                               // ORD 5
     616,                                                                         // ORD 6
 };
-constexpr bool tile_code_big(int code)
-{
-    for (int c : kTileBigCodes)
-        if (c == code) return true;
-    return false;
-}
-constexpr bool tile_big_codes_shipped()
-{
-    for (int c : kTileBigCodes)
-        if (!tile_code_shipped(c) || c >= 1000) return false;
-    return true;
-}
-static_assert(tile_big_codes_shipped(), "kTileBigCodes: a subset of kTileCodes, W = 1");
+constexpr bool tile_code_big(int code) { return tile_code_in(kTileBigCodes, code); }
+static_assert(tile_codes_shipped_w1(kTileBigCodes), "kTileBigCodes: a subset of kTileCodes, W = 1");
 
 // ---- the big form's window.  A tile at buffer row y0, tile_h rows high, run `turns` turns deep
 // touches only buffer rows (y0 - turns + j) mod modrows, j = 0 .. tile_h + 2 turns - 1.  With
@@ -494,14 +471,14 @@ inline TileGrid tile_grid_big(int nw, int rows, int turns, int tile_h, int tile_
 // ntx x nty of the resident kernels (K1p / K1q / K1r find their neighbours by tile index)
 long long tile_count(int nw, int rows, int tile_h, int tile_w, int seg, int turns = 0);
 hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s);
-// K1p k_tile_persist (gol_tile.h): `turns` turns in blocks of K on tiles resident for the whole
+// K1p k_tile_persist (gol_tile_lab.h): `turns` turns in blocks of K on tiles resident for the whole
 // launch, exchanging borders between blocks through u0 / u1 (uncached, board-sized) and
 // per-tile flags (uncached, one per tile; epoch above every earlier launch's flags).
 // tile_persist_ok: an instantiated code, K within the tile rows, every tile resident at once.
 bool tile_persist_ok(int nw, int rows, int turns, int K, int tile_h, int tile_w, int seg, int ncu);
 hipError_t launch_tile_persist(const StepArgs &a, int turns, int K, uint64_t *u0, uint64_t *u1,
                                unsigned *flags, unsigned epoch, hipStream_t s);
-// K1q k_tile_stream (gol_tile.h): `turns` turns in blocks of K over (block, tile) items taken
+// K1q k_tile_stream (gol_tile_lab.h): `turns` turns in blocks of K over (block, tile) items taken
 // from *counter (value `base` at the launch) by min(items, CUs x occupancy, max_grid if > 0)
 // workgroups, whose count goes to *grid (the counter advances by items + grid).  Same u0 / u1 / flags contract
 // as K1p; tile_stream_ok: an instantiated code and K within the tile rows (no residency need).
@@ -509,7 +486,7 @@ bool tile_stream_ok(int nw, int rows, int K, int tile_h, int tile_w, int seg);
 hipError_t launch_tile_stream(const StepArgs &a, int turns, int K, uint64_t *u0, uint64_t *u1,
                               unsigned *flags, unsigned epoch, unsigned *counter, unsigned base,
                               int ncu, int max_grid, unsigned *grid, hipStream_t s);
-// K1r k_tile_ring (gol_tile.h): K1p's contract (flags, epoch) with the tiles kept in registers
+// K1r k_tile_ring (gol_tile_lab.h): K1p's contract (flags, epoch) with the tiles kept in registers
 // across blocks; only their rings pass through u0 / u1 (uncached, board-sized).
 bool tile_ring_ok(int nw, int rows, int K, int tile_h, int tile_w, int seg, int ncu);
 // gcount (tools experiments, else nullptr): a grid-wide barrier per block on that counter,

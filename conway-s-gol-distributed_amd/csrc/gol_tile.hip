@@ -1,5 +1,17 @@
 // gol_tile.hip -- the k_step_tile instantiation table (K1t, gol_tile.h) and its launcher.
+// The tools build and two A/B builds (make variant VDEFS=-DGOL_TILE_PAIR=1, -DGOL_TILE_RAW=n) also
+// compile gol_tile_lab.h, the experiments' kernels and hooks, which documents those macros.
+// Their launchers are the tools region at the end of this file; their tables (persist_fn,
+// ring_fn, stream_fn) stand where they always stood, between the product tables, because the
+// order of the tables is the order of the kernels in the unit's code object, which the profiles
+// and the assembly comparison of DESIGN.md rely on.
+#if GOL_TOOLS || GOL_TILE_PAIR || GOL_TILE_RAW
+#define GOL_TILE_LAB 1
+#endif
 #include "gol_tile.h"
+#ifndef GOL_TILE_PAIR   // (no lab header in this build: the launcher below still asks)
+#define GOL_TILE_PAIR 0
+#endif
 
 #include <algorithm>
 #include <cstdio>
@@ -384,6 +396,9 @@ hipError_t launch_tile(const StepArgs &a, int turns, hipStream_t s)
 
 }  // namespace golk
 
+// ---- Tools region: the launchers of the kernels of gol_tile_lab.h (K1p k_tile_persist, K1r
+// k_tile_ring, K1q k_tile_stream).  A product build keeps these functions, which other units link
+// against; its tables above are empty, so every *_ok is false and every launch an error.
 namespace golk {
 
 bool tile_persist_ok(int nw, int rows, int turns, int K, int tile_h, int tile_w, int seg, int ncu)
@@ -423,10 +438,6 @@ hipError_t launch_tile_persist(const StepArgs &a, int turns, int K, uint64_t *u0
     void *params[] = {&in, &out, &u0, &u1, &args, &t, &k, &ntx_arg, &nt, &flags, &epoch};
     return hipLaunchKernel(fn, dim3(blocks), dim3(threads), params, tile_lds_bytes(threads, 1), s);
 }
-
-}  // namespace golk
-
-namespace golk {
 
 bool tile_ring_ok(int nw, int rows, int K, int tile_h, int tile_w, int seg, int ncu)
 {
