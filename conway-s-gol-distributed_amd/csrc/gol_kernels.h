@@ -218,6 +218,22 @@ hipError_t launch_step_multi(const StepArgs &a, int turns, hipStream_t s);
 // workgroup (a.counts: the counted form); hipErrorInvalidValue for a board, row range or depth
 // it does not run (gol_resident.h, resident_plan)
 hipError_t launch_resident(const StepArgs &a, int turns, hipStream_t s);
+// k_step_resident_batch (gol_resident.hip): `turns` turns (1 .. kResidentMaxTurns: one turn is
+// allowed here, the 2 of resident_turns_ok is the engine planner's rule) of `boards` torus boards
+// of width x height cells, board b at words + b x height x nw, one workgroup each, IN PLACE.
+// counts (nullable: the counted form): a ring of kResidentMaxTurns x boards uint32, the count
+// after turn t of board b at [(t % kResidentMaxTurns) x boards + b]; turn0 = the batch's turn
+// before the launch.  hipErrorInvalidValue for a shape resident_plan refuses, turns outside
+// 1 .. kResidentMaxTurns, boards < 1 and boards x height > INT32_MAX.
+hipError_t launch_resident_batch(uint64_t *words, uint32_t *counts, int width, int height,
+                                 int boards, long long turn0, int turns, hipStream_t s);
+// k_batch_alive: the alive cells of `boards` consecutive boards of board_words words each, one
+// wavefront per board, one uint32 per board
+hipError_t launch_batch_alive(const uint64_t *words, int board_words, int boards, uint32_t *out,
+                              hipStream_t s);
+// resident workgroups per CU of that shape's k_step_resident_batch (occupancy API: VGPRs, LDS;
+// 0 on error)
+int resident_batch_blocks_per_cu(int width, int height, bool cnt);
 // k_step_tile (gol_tile.hip): a launch of `turns` turns on tiles of band x tile_w words with
 // tile_seg rows per lane; shape check, workgroup waves, tile count
 constexpr int kTileMaxWavesHost = 16;  // k_step_tile: waves per workgroup (gol_tile.h)

@@ -27,6 +27,7 @@ from typing import Any, NamedTuple, Optional
 import numpy as np
 
 from . import _native as N
+from .batch import BatchEngine, BatchInfo  # noqa: F401
 from .engine import Engine, haloed_rows, strip_split  # noqa: F401
 
 
@@ -310,5 +311,5 @@ def Run(p: Params, events: Channel, keyPresses: Optional[Channel] = None, *,
 __all__ = [
     "Params", "Run", "RunHandle", "RunError", "Channel", "Cell", "State", "Event", "AliveCellsCount",
     "ImageOutputComplete", "StateChange", "CellFlipped", "TurnComplete", "FinalTurnComplete",
-    "Engine", "strip_split", "haloed_rows",
+    "Engine", "strip_split", "haloed_rows", "BatchEngine", "BatchInfo",
 ]

@@ -169,6 +169,22 @@ SIGNATURES = {
     "gol_halo_buffers": (_i32, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                 ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                 ctypes.POINTER(ctypes.c_int32)]),
+    "gol_batch_create": (_i32, [_i32, _i32, _i32, _i32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
+    "gol_batch_destroy": (None, [_vp]),
+    "gol_batch_last_error": (ctypes.c_char_p, [_vp]),
+    "gol_batch_get_info": (_i32, [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 7 + [_i64p]),
+    "gol_batch_occupancy": (_i32, [_vp, ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_int32)]),
+    "gol_batch_get_stream": (_vp, [_vp]),
+    "gol_batch_sync": (_i32, [_vp]),
+    "gol_batch_load_packed": (_i32, [_vp, _i32, _i32, _u64p]),
+    "gol_batch_load": (_i32, [_vp, _i32, _i32, _u8p]),
+    "gol_batch_fill_random": (_i32, [_vp, ctypes.c_uint64]),
+    "gol_batch_step": (_i32, [_vp, _i64]),
+    "gol_batch_read_packed": (_i32, [_vp, _i32, _i32, _u64p]),
+    "gol_batch_read": (_i32, [_vp, _i32, _i32, _u8p]),
+    "gol_batch_alive": (_i32, [_vp, _i32, _i32, _i64p]),
+    "gol_batch_turn_counts": (_i32, [_vp, _i64, _i64, _i64p]),
     "gol_run_start": (_i32, [ctypes.POINTER(gol_params), ctypes.POINTER(gol_run_options),
                              ctypes.POINTER(_vp)]),
     "gol_run_next_event": (_i32, [_vp, ctypes.POINTER(gol_event), _i32]),

@@ -432,6 +432,73 @@ int gol_halo_done(gol_ctx *ctx);
 int gol_halo_buffers(gol_ctx *ctx, void **send_top, void **send_bottom, void **recv_top,
                      void **recv_bottom, int32_t *layout);
 
+/* ------------------------------------------------------------------ Batch
+ * Many small boards in one launch (k_step_resident_batch).  A gol_batch owns `boards` torus
+ * boards of one shape, width x height cells each, in one device buffer: board i's rows follow
+ * board i - 1's, height x ceil(width / 64) words per board in the standard layout.  A step runs
+ * ceil(turns / 256) launches of near-equal depth, each with one workgroup per board that keeps
+ * its board in registers for the launch's turns (the partition of gol_resident_plan) and writes
+ * it back in place: the batch has one buffer, no double buffer.  No reference counterpart (its
+ * Server runs one board).
+ *
+ * Eligible shapes are gol_resident_plan's and nothing else -- width 2 .. 255, height at most
+ * 4096 / 2048 / 1280 / 1024 rows at 1 .. 4 words per row; there is no fallback kernel -- with
+ * boards >= 1 and boards x height <= INT32_MAX.  flags: 0 or GOL_FLAG_COUNT_EVERY_TURN (any
+ * other bit: GOL_EINVAL).  device: -1 = the current device.  Arguments are checked before the
+ * device is looked for: GOL_EINVAL, then GOL_ENODEV, then GOL_ENOMEM.  A new batch holds dead
+ * boards at turn 0.
+ *
+ * Threading: one thread drives a batch.  There are no cross-thread services and no control
+ * word.  Every call on a NULL handle returns GOL_EINVAL; gol_batch_last_error(NULL) is "". */
+typedef struct gol_batch gol_batch;
+int  gol_batch_create(int32_t width, int32_t height, int32_t boards, int32_t device,
+                      uint32_t flags, gol_batch **out);
+void gol_batch_destroy(gol_batch *b);
+const char *gol_batch_last_error(const gol_batch *b);
+/* The shape, the partition every board runs on (gol_resident_plan) and the turn.  Any
+ * out-pointer may be NULL. */
+int  gol_batch_get_info(gol_batch *b, int32_t *width, int32_t *height, int32_t *boards,
+                        int32_t *words_per_row, int32_t *lanes, int32_t *rows_per_lane,
+                        int32_t *waves, int64_t *turn);
+/* How many of the batch's workgroups one launch keeps resident at once: *blocks_per_cu (the
+ * occupancy the HIP runtime reports for this batch's kernel) on each of *cus compute units.  A
+ * batch of more boards runs in rounds; results never depend on it (introspection for tests and
+ * tools/batch_speed.py). */
+int  gol_batch_occupancy(gol_batch *b, int32_t *blocks_per_cu, int32_t *cus);
+/* The batch's own HIP stream, on which all its work is queued (for a caller that records events
+ * around a step or orders other work after it); NULL for a NULL handle. */
+void *gol_batch_get_stream(gol_batch *b);
+int  gol_batch_sync(gol_batch *b);
+/* Loads work on boards first .. first + n - 1 (n >= 1; a range outside the batch: GOL_EINVAL,
+ * nothing changed) and leave the other boards as they are.  A load of the whole batch sets the
+ * turn to 0; a partial load keeps it, so a caller can re-seed extinct boards mid-run.  While
+ * counts are recorded, the count ring still holds what the board's previous occupant had at the
+ * recorded turns: the entries of a partially loaded board before its load are the caller's
+ * concern.
+ * gol_batch_load_packed: n x height x words_per_row words.  gol_load_packed's padding rule
+ * holds: a set bit past `width` in a row's last word returns GOL_EINVAL, gol_batch_last_error
+ * names the board and the row, and nothing is copied.
+ * gol_batch_load: n x height x width bytes, 255 = alive, anything else = dead (no non-binary
+ * semantics, as gol_write_window).
+ * gol_batch_fill_random: board i, row y = row i x height + y of what gol_fill_random(seed) gives
+ * a board of width x (boards x height) cells; sets the turn to 0. */
+int  gol_batch_load_packed(gol_batch *b, int32_t first, int32_t n, const uint64_t *words);
+int  gol_batch_load(gol_batch *b, int32_t first, int32_t n, const uint8_t *bytes);
+int  gol_batch_fill_random(gol_batch *b, uint64_t seed);
+/* Advance every board `turns` turns (>= 0).  Asynchronous: the read-outs and gol_batch_sync
+ * wait for it. */
+int  gol_batch_step(gol_batch *b, int64_t turns);
+/* Boards first .. first + n - 1 as n x height x words_per_row packed words (zero padding), as
+ * n x height x width bytes (0 / 255), and as one alive count per board. */
+int  gol_batch_read_packed(gol_batch *b, int32_t first, int32_t n, uint64_t *out);
+int  gol_batch_read(gol_batch *b, int32_t first, int32_t n, uint8_t *out);
+int  gol_batch_alive(gol_batch *b, int32_t first, int32_t n, int64_t *out);
+/* Per-turn alive counts of a GOL_FLAG_COUNT_EVERY_TURN batch (else GOL_ESTATE): n x boards
+ * entries, turn the major index, the counts after turns first_turn .. first_turn + n - 1.  Those
+ * turns must be among the last 256 stepped turns (turn - 255 .. turn, and at least 1) and stepped
+ * since the last whole-batch load, else GOL_EINVAL. */
+int  gol_batch_turn_counts(gol_batch *b, int64_t first_turn, int64_t n, int64_t *out);
+
 /* -------------------------------------------------------------- run driver */
 typedef struct gol_params {          /* Local/gol/gol.go:4-9 */
     int64_t turns;
