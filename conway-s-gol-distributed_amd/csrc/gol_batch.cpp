@@ -4,9 +4,13 @@
 // (gol_resident.hip).  One thread drives a batch: no lock, no cross-thread services, no control
 // word.  The boards are stepped in place (one buffer, no double buffer), so nothing here needs a
 // "current half".
+// K1r2s, the "Settle" section: gol_settle_step advances the same boards with
+// k_settle_resident_batch (gol_settle.hip), which watches every board for its period; the watch's
+// state (one SettleState and one snapshot per board) is allocated at the first gol_settle_step.
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -14,6 +18,7 @@
 
 #include "gol_ctx.h"
 #include "gol_resident.h"
+#include "gol_settle.h"
 
 using goleng::DeviceGuard;
 
@@ -27,6 +32,9 @@ struct gol_batch {
     uint32_t *counts = nullptr;              // GOL_FLAG_COUNT_EVERY_TURN: [turn % 256][board]
     uint32_t *alive = nullptr;               // gol_batch_alive: one count per board (first call on)
     long long turn = 0;                      // completed turns since the last whole-batch load
+    uint64_t *snaps = nullptr;               // gol_settle_step: a snapshot per board (first call on)
+    golk::SettleState *states = nullptr;     //   and its watch
+    bool watching = false;                   // a watch is on: since a gol_settle_step, until a reset
     std::string err;
     void *staging = nullptr;                 // page-locked host memory, grows on demand
     size_t staging_size = 0;
@@ -81,9 +89,39 @@ int chunk_boards(const gol_batch *b, int32_t n)
     return (int)std::max<size_t>(1, std::min<size_t>(per, (size_t)n));
 }
 
-void loaded(gol_batch *b, int32_t first, int32_t n)
+// the watch of boards first .. first + n - 1 begins at the batch's turn, with snapshot 0 = the
+// boards as they are (queued on the batch's stream)
+int watch_from_here(gol_batch *b, int32_t first, int32_t n)
 {
-    if (first == 0 && n == b->boards) b->turn = 0;
+    const size_t bw = b->board_words();
+    BATCH_HIP(b, hipMemcpyAsync(b->snaps + (size_t)first * bw, b->words + (size_t)first * bw,
+                                (size_t)n * bw * 8, hipMemcpyDeviceToDevice, b->stream));
+    BATCH_HIP(b, golk::launch_settle_init(b->states, first, n, b->turn, b->stream));
+    return GOL_OK;
+}
+
+// after a load of boards first .. first + n - 1: a whole-batch load sets the turn to 0 and ends
+// the watch; a partial load under a watch restarts the watch of its boards
+int loaded(gol_batch *b, int32_t first, int32_t n)
+{
+    if (first == 0 && n == b->boards) {
+        b->turn = 0;
+        b->watching = false;
+        return GOL_OK;
+    }
+    if (!b->watching) return GOL_OK;
+    if (int rc = watch_from_here(b, first, n)) return rc;
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+// GOL_SETTLE_DEPTH=D in the environment (read at every gol_settle_step): launches of at most D
+// turns, 1 .. kSettleMaxDepth; anything else: kSettleMaxDepth
+int settle_depth()
+{
+    const char *v = getenv("GOL_SETTLE_DEPTH");
+    const int d = v ? atoi(v) : 0;
+    return d >= 1 && d <= golk::kSettleMaxDepth ? d : golk::kSettleMaxDepth;
 }
 
 }  // namespace
@@ -143,6 +181,8 @@ void gol_batch_destroy(gol_batch *b)
         if (b->words) (void)hipFree(b->words);
         if (b->counts) (void)hipFree(b->counts);
         if (b->alive) (void)hipFree(b->alive);
+        if (b->snaps) (void)hipFree(b->snaps);
+        if (b->states) (void)hipFree(b->states);
         if (b->staging) (void)hipHostFree(b->staging);
         if (b->stream) (void)hipStreamDestroy(b->stream);
     }
@@ -211,8 +251,7 @@ int gol_batch_load_packed(gol_batch *b, int32_t first, int32_t n, const uint64_t
     BATCH_HIP(b, hipMemcpyAsync(b->words + (size_t)first * bw, words, (size_t)n * bw * 8,
                                 hipMemcpyHostToDevice, b->stream));
     BATCH_HIP(b, hipStreamSynchronize(b->stream));
-    loaded(b, first, n);
-    return GOL_OK;
+    return loaded(b, first, n);
 }
 
 int gol_batch_load(gol_batch *b, int32_t first, int32_t n, const uint8_t *bytes)
@@ -240,8 +279,7 @@ int gol_batch_load(gol_batch *b, int32_t first, int32_t n, const uint8_t *bytes)
                                     hipMemcpyHostToDevice, b->stream));
         BATCH_HIP(b, hipStreamSynchronize(b->stream));      // (the staging area is reused)
     }
-    loaded(b, first, n);
-    return GOL_OK;
+    return loaded(b, first, n);
 }
 
 int gol_batch_fill_random(gol_batch *b, uint64_t seed)
@@ -254,12 +292,14 @@ int gol_batch_fill_random(gol_batch *b, uint64_t seed)
                                           b->stream));
     BATCH_HIP(b, hipStreamSynchronize(b->stream));
     b->turn = 0;
+    b->watching = false;
     return GOL_OK;
 }
 
 int gol_batch_step(gol_batch *b, int64_t turns)
 {
     if (!b || turns < 0) return GOL_EINVAL;
+    b->watching = false;
     DeviceGuard g(b->device);
     // ceil(turns / 256) launches of near-equal depth (plan_launch's split)
     for (int64_t left = turns; left > 0;) {
@@ -352,6 +392,54 @@ int gol_batch_turn_counts(gol_batch *b, int64_t first_turn, int64_t n, int64_t *
     for (int64_t i = 0; i < n; ++i) {
         const size_t slot = (size_t)((first_turn + i) % golk::kResidentMaxTurns);
         for (int k = 0; k < b->boards; ++k) out[(size_t)i * b->boards + k] = h[slot * b->boards + k];
+    }
+    return GOL_OK;
+}
+
+// ---------------------------------------------------------------- Settle
+int gol_settle_step(gol_batch *b, int64_t turns)
+{
+    if (!b || turns < 0) return GOL_EINVAL;
+    if (b->counts)
+        return bfail(b, GOL_ESTATE, "gol_settle_step: the batch records per-turn counts "
+                                    "(GOL_FLAG_COUNT_EVERY_TURN); use gol_batch_step");
+    DeviceGuard g(b->device);
+    if (!b->snaps)
+        BATCH_HIP(b, hipMalloc((void **)&b->snaps, (size_t)b->boards * b->board_words() * 8));
+    if (!b->states)
+        BATCH_HIP(b, hipMalloc((void **)&b->states, (size_t)b->boards * sizeof(golk::SettleState)));
+    if (!b->watching) {
+        if (int rc = watch_from_here(b, 0, b->boards)) return rc;
+        b->watching = true;
+    }
+    const int depth = settle_depth();
+    for (int64_t left = turns; left > 0;) {
+        const int k = golk::settle_next_depth(left, depth);
+        BATCH_HIP(b, golk::launch_settle_batch(b->words, b->snaps, b->states, b->width, b->height,
+                                               b->boards, b->turn, k, b->stream));
+        b->turn += k;
+        left -= k;
+    }
+    return GOL_OK;
+}
+
+int gol_settle_read(gol_batch *b, int32_t first, int32_t n, int64_t *settled_turn, int64_t *period)
+{
+    if (!b) return GOL_EINVAL;
+    if (!range_ok(b, first, n))
+        return bfail(b, GOL_EINVAL, "gol_settle_read: boards %d .. %lld are not in a batch of %d", first,
+                     (long long)first + n - 1, b->boards);
+    if (!b->watching)
+        return bfail(b, GOL_ESTATE, "gol_settle_read: no watch is on (gol_settle_step starts one)");
+    DeviceGuard g(b->device);
+    if (int rc = ensure_staging(b, (size_t)n * sizeof(golk::SettleState))) return rc;
+    BATCH_HIP(b, hipMemcpyAsync(b->staging, b->states + first, (size_t)n * sizeof(golk::SettleState),
+                                hipMemcpyDeviceToHost, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    const golk::SettleState *h = (const golk::SettleState *)b->staging;
+    for (int32_t i = 0; i < n; ++i) {
+        if (settled_turn) settled_turn[i] = h[i].settled_turn;
+        if (period) period[i] = h[i].period;
     }
     return GOL_OK;
 }

@@ -234,6 +234,16 @@ hipError_t launch_batch_alive(const uint64_t *words, int board_words, int boards
 // resident workgroups per CU of that shape's k_step_resident_batch (occupancy API: VGPRs, LDS;
 // 0 on error)
 int resident_batch_blocks_per_cu(int width, int height, bool cnt);
+// k_settle_resident_batch (gol_settle.hip, gol_settle.h): launch_resident_batch's boards and
+// checks (no counted form), `turns` 1 .. kSettleMaxDepth, with every board under the watch
+// states[b] and its snapshot at snaps + b x height x nw; turn0 = the batch's turn before the
+// launch, not reduced.
+struct SettleState;
+hipError_t launch_settle_batch(uint64_t *words, uint64_t *snaps, SettleState *states, int width,
+                               int height, int boards, long long turn0, int turns, hipStream_t s);
+// k_settle_init: the watch of boards first .. first + n - 1 begins at `turn` (unknown period,
+// snapshot 0 held: the caller copies the boards' words to their snapshots)
+hipError_t launch_settle_init(SettleState *states, int first, int n, long long turn, hipStream_t s);
 // k_step_tile (gol_tile.hip): a launch of `turns` turns on tiles of band x tile_w words with
 // tile_seg rows per lane; shape check, workgroup waves, tile count
 constexpr int kTileMaxWavesHost = 16;  // k_step_tile: waves per workgroup (gol_tile.h)

@@ -185,6 +185,9 @@ SIGNATURES = {
     "gol_batch_read": (_i32, [_vp, _i32, _i32, _u8p]),
     "gol_batch_alive": (_i32, [_vp, _i32, _i32, _i64p]),
     "gol_batch_turn_counts": (_i32, [_vp, _i64, _i64, _i64p]),
+    "gol_settle_step": (_i32, [_vp, _i64]),
+    "gol_settle_read": (_i32, [_vp, _i32, _i32, _i64p, _i64p]),
+    "gol_settle_host_run": (_i32, [_u64p, _i32, _i32, _i64, _i32, _u64p, _i64p, _i64p]),
     "gol_run_start": (_i32, [ctypes.POINTER(gol_params), ctypes.POINTER(gol_run_options),
                              ctypes.POINTER(_vp)]),
     "gol_run_next_event": (_i32, [_vp, ctypes.POINTER(gol_event), _i32]),

@@ -2,8 +2,10 @@
 
 Many torus boards of one shape narrower than 256 cells in one device buffer, every step one
 k_step_resident_batch launch per 256 turns with one workgroup per board -- what a soup search, a
-rule statistic or a sweep over seeds runs thousands of.  No reference counterpart: its Server
-runs one board.
+rule statistic or a sweep over seeds runs thousands of.  step_settle() is the same step with a
+watch on every board (k_settle_resident_batch): settled() gives each board's period and the turn
+it was found at, and a board known to repeat skips its settled turns.  No reference counterpart:
+its Server runs one board.
 """
 from __future__ import annotations
 
@@ -122,6 +124,21 @@ class BatchEngine:
 
     def step(self, turns: int = 1):
         self._c(self._L.gol_batch_step(self._h, int(turns)))
+
+    def step_settle(self, turns: int = 1):
+        """step(), watching every board for its period and skipping the turns of a board known
+        to repeat (include/gol_amd.h, "Settle"); the boards end where step() puts them."""
+        self._c(self._L.gol_settle_step(self._h, int(turns)))
+
+    def settled(self, first: int = 0, n: int | None = None):
+        """(settled_turn, period) of boards first .. first + n - 1 as int64 arrays: -1 and 0
+        while a board's period is unknown."""
+        first, n = self._range(first, n)
+        turn = np.zeros(max(n, 1), dtype=np.int64)
+        period = np.zeros(max(n, 1), dtype=np.int64)
+        self._c(self._L.gol_settle_read(self._h, first, n, turn.ctypes.data_as(N._i64p),
+                                        period.ctypes.data_as(N._i64p)))
+        return turn[:n], period[:n]
 
     def read_packed(self, first: int = 0, n: int | None = None) -> np.ndarray:
         first, n = self._range(first, n)

@@ -499,6 +499,53 @@ int  gol_batch_alive(gol_batch *b, int32_t first, int32_t n, int64_t *out);
  * since the last whole-batch load, else GOL_EINVAL. */
 int  gol_batch_turn_counts(gol_batch *b, int64_t first_turn, int64_t n, int64_t *out);
 
+/* ------------------------------------------------------------------ Settle
+ * Find the period of every board of a batch on the device, and skip the turns of a board known to
+ * repeat (k_settle_resident_batch).  A batch can WATCH its boards.  While board i is watched from
+ * turn start_i, the batch keeps a snapshot of it, taken at turns s_k = start_i + 2^k - 1, k = 0,
+ * 1, 2, ... (Brent's schedule).  After every watched turn t the board is compared with its
+ * current snapshot, every word of every row; at t == s_k + 2^k the compare comes first, and a
+ * board that does not match becomes snapshot k + 1.  The first match gives period = t - s_k and
+ * settled_turn = t.  That period is the minimal period of the cycle the board has entered: with
+ * mu the first turn of the cycle, settled_turn = s_k + period for the least k with s_k >= mu and
+ * 2^k >= period.  After its match a board is watched no more, and every later advance of d turns
+ * runs d mod period turns on it (the rest of the launch the match was found in included).  A dead
+ * board has period 1.  Neither the entries nor the boards depend on how a step is cut into
+ * launches or on how many boards are resident at once.
+ *
+ * All boards of a batch stay at the batch's one turn: after gol_settle_step(b, n) every read-out
+ * (gol_batch_read*, gol_batch_alive) equals what gol_batch_step(b, n) gives.
+ *
+ * gol_settle_step: advance every board `turns` turns (>= 0) like gol_batch_step, asynchronous
+ * like it, watching as above.  The first call after a reset (below) starts the watch of every
+ * board at the batch's turn then, with snapshot 0 = the board as it is; the watch's device
+ * buffers (a snapshot and 32 bytes per board) are allocated at the first call.  A step runs
+ * launches of at most 256 turns; GOL_SETTLE_DEPTH=D in the environment, read at every call,
+ * makes that 1 .. 256 (tests put launch boundaries at every phase of the schedule with it).
+ * turns < 0 or a NULL handle: GOL_EINVAL.  A batch created with GOL_FLAG_COUNT_EVERY_TURN:
+ * GOL_ESTATE, and nothing runs (the per-turn count of a skipped turn is not recorded).
+ *
+ * gol_settle_read: one entry per board of first .. first + n - 1 (gol_batch_alive's range rule):
+ * period 0 and settled_turn -1 while unknown.  Either out-pointer may be NULL.  GOL_ESTATE if no
+ * watch is on.
+ *
+ * Resets: gol_batch_step, gol_batch_fill_random and a load of the whole batch end the watch of
+ * all boards and forget their periods (the three calls themselves behave as without a watch); the
+ * next gol_settle_step starts anew.  A partial load made while a watch is on restarts the watch
+ * of the loaded boards at the batch's current turn; the other boards keep theirs. */
+int  gol_settle_step(gol_batch *b, int64_t turns);
+int  gol_settle_read(gol_batch *b, int32_t first, int32_t n, int64_t *settled_turn,
+                     int64_t *period);
+/* The host build of k_settle_resident_batch for one board: the kernel's own functions run lane
+ * by lane on arrays indexed like its LDS areas, the waves' compare words, the reload of the state
+ * at every launch and the skip of settled turns included (as gol_resident_host_run is for
+ * k_step_resident).  `turns` turns from turn 0 in launches of at most `depth` turns (1 .. 256),
+ * the watch starting at turn 0.  in / out: height x ceil(width / 64) words.  settled_turn and
+ * period (either may be NULL) as gol_settle_read.  GOL_EINVAL for NULL in / out, turns < 0, a
+ * depth outside 1 .. 256 and a shape gol_resident_plan refuses.  Needs no device. */
+int  gol_settle_host_run(const uint64_t *in, int32_t width, int32_t height, int64_t turns,
+                         int32_t depth, uint64_t *out, int64_t *settled_turn, int64_t *period);
+
 /* -------------------------------------------------------------- run driver */
 typedef struct gol_params {          /* Local/gol/gol.go:4-9 */
     int64_t turns;
